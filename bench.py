@@ -5,11 +5,19 @@ BASELINE.json metric: "pattern lookups/s + achieved HBM GB/s, 2^30-byte text,
 GPU (inputs already resident in HBM), through the C ABI (sas_search_fixed).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--algo prefix|plain|quad|...]
+                    [--dump-outputs DIR] [--full]
         (N > 1: bench.py starts N rank processes itself, one per GPU, benchlib/launch.py)
     torchrun --nproc-per-node N bench.py --gpus N ...   (the same N ranks from a launcher)
 
 One JSON line.  `value` is the headline algorithm (PREFIX: a p = 16-char bucket table with
-32-B inline entries over fused quad leaves) on the configs[1]/[2] workload; `configs` holds
+32-B inline entries over fused quad leaves) on the configs[1]/[2] workload.  A plain run
+builds the index, cuts the queries, runs W untimed and K timed steps and prints the line
+(`value`, `ms_per_step` = the host clock over the K steps / K); --dump-outputs DIR then
+writes the positions of the last timed step (DIR/positions.npy, float64, a fixed seeded
+sample of the 10^7; text and queries are seeded: the same arguments give the same inputs).
+Everything else is --full's: the correctness guard, the roofline (its probe-count pass and
+PMC summary), the CPU baselines, the host-buffer pass, the other algorithms, occurrence
+ranges, the detail file and `configs`, which holds
 one sub-record per BASELINE config, each with its own algorithm, index size, bytes per
 lookup split by where they are served (HBM / Infinity-Cache-resident arrays / LDS), PMC
 traffic where a committed --pmc pass exists, and ns per lookup:
@@ -61,6 +69,13 @@ def main():
                          "(benchlib/launch.py); under torchrun it must equal WORLD_SIZE (default: WORLD_SIZE, else 1)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="c1 workload: beside the headline, the correctness guard, the roofline, the CPU baselines, "
+                         "the host-buffer pass, every variant and every config's sub-record (the --no-* switches "
+                         "trim this run); without it the run times the headline's steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="c1 workload: after the timed steps write the last step's positions to DIR/positions.npy "
+                         "(float64; above 4M queries a fixed seeded sample of them)")
     ap.add_argument("--n", type=int, default=1 << 30, help="text length (chars)")
     ap.add_argument("--nq", type=int, default=10_000_000, help="queries per GPU")
     ap.add_argument("--m", type=int, default=32, help="query length")
@@ -120,6 +135,10 @@ def main():
                          "ranges with RCCL all-to-all query routing (SURVEY §8e)")
     ap.add_argument("--probe-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload != "c1":
+        ap.error("--dump-outputs writes the c1 workload's positions")
     # --gpus N without a launcher: N fresh rank processes, started before this process makes
     # any HIP call; rank 0 prints the line, the job fails if any rank does
     if needs_spawn(args.gpus):
@@ -238,13 +257,18 @@ def main():
     if args.mode == "shard":
         engine.assert_no_overflow()
     log(f"headline {args.algo}: {kernel_ms:.3f} ms per {nq}")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's positions, one per query
+        log(f"outputs in {args.dump_outputs}: {dump_outputs(torch, args.dump_outputs, {'positions': out})}")
+    full = args.full  # everything below the headline's own figure
     # correctness guard (untimed): every answer is an occurrence of its query, and a sample
     # is proven an exact lower bound on the index's own SA
-    occ = text[(out[:, None] + ar[None, :]).reshape(-1).clamp_(max=n - 1)]
-    if not bool(torch.equal(occ, qbytes)):
-        raise SystemExit(f"bench: {args.algo} returned a non-occurrence position")
-    del occ
-    whole = args.mode == "replicated" or ws == 1
+    if full:
+        occ = text[(out[:, None] + ar[None, :]).reshape(-1).clamp_(max=n - 1)]
+        if not bool(torch.equal(occ, qbytes)):
+            raise SystemExit(f"bench: {args.algo} returned a non-occurrence position")
+        del occ
+    whole = full and (args.mode == "replicated" or ws == 1)
     proven = 0
     if whole:
         rng = np.random.default_rng(11 + rank)
@@ -264,7 +288,7 @@ def main():
     # caller handing host memory through the C ABI sees it (pinned staging, chunked
     # H2D / kernel / D2H over 3 streams, csrc/host_stage.hpp).  Never `value`.
     e2e = None
-    if args.mode == "replicated" and not args.no_e2e:
+    if full and args.mode == "replicated" and not args.no_e2e:
         hq = qbytes.cpu().numpy()
         ref_host = out.cpu().numpy().astype(np.uint64)
         # the caller's result array is allocated and touched once and reused, as a caller
@@ -291,7 +315,7 @@ def main():
     headline_pos = out.clone()
     variants = {}
     vout = torch.empty_like(out)
-    for v in [x for x in args.variants.split(",") if x and x != args.algo and args.mode == "replicated"]:
+    for v in [x for x in args.variants.split(",") if x and x != args.algo and args.mode == "replicated" and full]:
         # every variant is timed like the headline: the driver's steps and warmup
         vsteps = args.steps
         vel, vk, vmed = run_algo(v, vsteps, args.warmup, vout)
@@ -347,7 +371,7 @@ def main():
     # LLCP at m = 64..256 on this random text now, on a repetitive text after this index is
     # freed (below); N = 1 only
     lcp_long = None
-    if ws == 1 and args.mode == "replicated" and not args.no_lcp_long and stats["llcp_bytes"]:
+    if full and ws == 1 and args.mode == "replicated" and not args.no_lcp_long and stats["llcp_bytes"]:
         lcp_long = {"what": "PLAIN vs mlr LCP vs Manber-Myers LLCP skipping vs the S-tree + LLCP tail (configs[2]'s "
                             "combination) vs QUAD, 10^7 positive len-m queries, kernel ms (HIP events), positions "
                             "identical; random: the headline's 2^30 text; repetitive: 2^24 random chars x 64 copies, "
@@ -360,7 +384,7 @@ def main():
     # checked: every positive query occurs, SA[lo] is the headline's position, and the
     # two kernels agree
     ranges = None
-    if args.mode == "replicated":
+    if full and args.mode == "replicated":
         def time_ranges(fl):
             res = {}
 
@@ -391,15 +415,18 @@ def main():
 
     pe = prefix_entry_bytes(stats) if stats["prefix_chars"] else 0
     pkey = str(stats["prefix_chars"]) + {16: "i", 32: "d", 64: "q"}.get(pe, "")
-    hpmc = load_pmc(f"{args.algo}{pkey if args.algo == 'prefix' else ''}_n{n}_q{nq}_m{m}")
-    hbpl = bytes_per_lookup(args.algo, stats, n, m, mean_probes)
-    head = record(args.algo, nq, kernel_ms, el, hbpl, footprint(args.algo, stats), hpmc, mean_probes,
-                  {"kernel_ms_median": kernel_med, "timed_launches": args.steps})
-    achieved = head["achieved_hbm_GBps"]
+    # the roofline needs the probe-count pass above and reads the PMC summary: --full's
+    hpmc = hbpl = head = achieved = None
+    if full:
+        hpmc = load_pmc(f"{args.algo}{pkey if args.algo == 'prefix' else ''}_n{n}_q{nq}_m{m}")
+        hbpl = bytes_per_lookup(args.algo, stats, n, m, mean_probes)
+        head = record(args.algo, nq, kernel_ms, el, hbpl, footprint(args.algo, stats), hpmc, mean_probes,
+                      {"kernel_ms_median": kernel_med, "timed_launches": args.steps})
+        achieved = head["achieved_hbm_GBps"]
 
     cpu = None
     configs = {}
-    if rank == 0 and ws == 1 and not args.no_cpu and args.mode == "replicated":
+    if full and rank == 0 and ws == 1 and not args.no_cpu and args.mode == "replicated":
         cpu = cpu_baseline(text, idx, qbytes, m, nq, args.cpu_seconds)
         cpos = cpu.pop("_pos")
         cpu["agrees_with_gpu"] = bool(np.array_equal(cpos, headline_pos[:len(cpos)].cpu().numpy().astype(np.uint64)))
@@ -455,18 +482,18 @@ def main():
         lcp_long["summary"] = lcp_long_summary(lcp_long)
         log("lcp_long done")
     # the u32 static-search-tree path (the reference's other crate, sst/bin/bench.rs:548-599): N = 1
-    if ws == 1 and not args.no_sst and args.mode == "replicated":
+    if full and ws == 1 and not args.no_sst and args.mode == "replicated":
         configs["sst"] = sst_record(args, torch, sas_amd, dev)
         log(f"sst done: best {configs['sst']['best']}")
     # configs[3]: free the 2^30 index first (N = 1 only: the scaling runs time the headline)
-    if ws == 1 and not args.no_c3 and args.mode == "replicated":
+    if full and ws == 1 and not args.no_c3 and args.mode == "replicated":
         idx.free()
         del text, qbytes, out, headline_pos, vout, off_t, packed
         torch.cuda.empty_cache()
         configs["c3"] = c3_record(args, torch, sas_amd, dev, rank)
         log("c3 done")
     # configs[4]: the sharded-text step on every rank (the driver's 1/2/4/8-GPU runs time it)
-    if not args.no_c4 and args.mode == "replicated":
+    if full and not args.no_c4 and args.mode == "replicated":
         idx.free()  # idempotent: the c3 block may have freed it already
         torch.cuda.empty_cache()
         configs["c4"] = c4_record(args, torch, sas_amd, dev, ws, rank, dist)
@@ -489,13 +516,13 @@ def main():
                        "index_bytes": footprint(args.algo, stats),
                        "index_bytes_per_text_char": _r(footprint(args.algo, stats) / n),
                        "built_index_bytes": stats["index_bytes"], "prefix_bytes": stats["prefix_bytes"],
-                       "ns_per_lookup": head["ns_per_lookup"], "mode": args.mode,
+                       "ns_per_lookup": kernel_ms * 1e6 / nq, "mode": args.mode,
                        "parallelism": (f"replicated index x{ws}, query shards (no data-path collective)"
                                        if args.mode == "replicated" else
                                        f"SA rank ranges over {ws} GPUs, sas_route + RCCL all_to_all_single "
                                        f"(queries out, positions back)")},
             # shard mode: the events bracket route + exchanges + search, not one kernel
-            "roofline": None if args.mode != "replicated" else {
+            "roofline": None if args.mode != "replicated" or not full else {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBPS,
                 "traffic": (head.get("pmc") or {}).get("fabric_bytes_per_lookup"),
@@ -519,16 +546,17 @@ def main():
             "configs": configs,
             "variants": variants,
             "index": idx_stats,
-            "setup_s": build_s, "verified": True,
-            "verification": f"every answer an occurrence; {proven} sampled answers proven exact lower bounds on the "
-                            f"index's SA; every variant bit-identical to the headline"
-                            + ("; CPU restatement identical on its sample" if cpu else ""),
+            "setup_s": build_s, "verified": full,
+            "verification": (f"every answer an occurrence; {proven} sampled answers proven exact lower bounds on the "
+                             f"index's SA; every variant bit-identical to the headline"
+                             + ("; CPU restatement identical on its sample" if cpu else ""))
+            if full else "none in a plain run: --full checks the positions, --dump-outputs writes them",
         }
         if lcp_long is not None:
             line["lcp_long"] = lcp_long
-        line["detail"] = write_detail(line, args.detail) if args.detail else None
+        line["detail"] = write_detail(line, args.detail) if args.detail and full else None
         short = compact_line(line)
-        log(f"result line {len(json.dumps(short))} B; full record {args.detail}")
+        log(f"result line {len(json.dumps(short))} B; full record {line['detail']}")
         emit(short)
     if dist is not None:
         dist.barrier()

@@ -83,6 +83,29 @@ def launch_times(torch, step, steps: int, warmup: int, stream, sync=None, barrie
     return {"mean_ms": evs[0].elapsed_time(evs[steps]) / steps, "median_ms": float(np.median(per)), "wall_s": el}
 
 
+DUMP_LIMIT = 64 << 20  # bytes: every array of one --dump-outputs directory together
+
+
+def dump_outputs(torch, dirpath: str, arrays: dict, seed: int = SEED) -> dict:
+    """--dump-outputs: each named result tensor of the last timed step as
+    <dirpath>/<name>.npy in float64 (positions are below 2^53: exact).  The arrays share
+    half of DUMP_LIMIT; one too large for its share is cut to a sorted sample of its
+    elements drawn without replacement from default_rng(seed), the same elements in every
+    run and every build.  Returns {name: elements written}."""
+    os.makedirs(dirpath, exist_ok=True)
+    keep = DUMP_LIMIT // 2 // 8 // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = a.reshape(-1)
+        if a.numel() > keep:
+            ids = np.sort(np.random.default_rng(seed).choice(a.numel(), size=keep, replace=False))
+            a = a[torch.from_numpy(ids).to(a.device)]
+        h = a.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(dirpath, f"{name}.npy"), h)
+        written[name] = int(h.size)
+    return written
+
+
 _RESULT_OUT = None
 
 

@@ -2,6 +2,8 @@
 exact lower bounds and rejects any other occurrence of a repeated query, on an
 oracle-backed stand-in index; bytes_per_lookup never charges LDS- or cache-served tree
 levels to HBM."""
+import os
+
 import numpy as np
 
 import bench
@@ -150,6 +152,23 @@ def test_pmc_attached_only_for_the_same_source_hash(tmp_path, monkeypatch):
     assert r["pmc"]["fabric_bytes_per_lookup"] == 1e8
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: float64 .npy files of at most DUMP_LIMIT bytes together; an array
+    over its share is cut to the same sorted sample of its elements in every run, a small
+    one is written whole and in order; values above 2^32 survive exactly."""
+    import torch
+    big = torch.arange(5_000_000, dtype=torch.int64) * 3 + (1 << 40)
+    small = torch.tensor([5, 1, 7], dtype=torch.int64)
+    for d in ("a", "b"):
+        w = bench.dump_outputs(torch, str(tmp_path / d), {"positions": big, "few": small})
+    a, b = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "b" / "positions.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert w == {"positions": a.size, "few": 3} and a.size == bench.DUMP_LIMIT // 2 // 8 // 2
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT
+    assert np.all(np.diff(a) > 0) and np.all((a - 2.0 ** 40) % 3 == 0) and a[-1] > 2.0 ** 40
+    assert np.load(tmp_path / "a" / "few.npy").tolist() == [5.0, 1.0, 7.0]
+
+
 def test_reference_sweep_sizes():
     """sizes() of sst/bin/bench.rs:453-471: 2^5 .. 2^to bytes, dense adds 5/4, 3/2, 7/4."""
     assert bench.ref_sizes(5, 8) == [32, 64, 128, 256]
@@ -240,6 +259,23 @@ def test_result_line_is_compact_and_complete():
         assert set(line["configs"][c]) >= {"lookups_per_s", "kernel_ms", "frac", "index_bytes"}
     assert "variants" not in line and "index" not in line
     assert json.loads(text) == line
+
+
+def test_plain_run_line_keeps_the_contract_keys():
+    """A run without --full has no roofline, CPU baseline, configs or detail file: the line
+    still carries every contract key, with the headline's figures as measured."""
+    import json
+    full = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "bench_record_r3.json")))
+    plain = dict(full, roofline=None, cpu_baseline=None, configs={}, variants={}, e2e_host=None,
+                 occurrence_ranges=None, verified=False, detail=None)
+    line = bench.compact_line(plain)
+    for k in REQUIRED:
+        assert k in line, k
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["configs"] == {}
+    assert line["verified"] is False and line["detail"] is None
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert line[k] == full[k], k
+    assert line["value"] == bench._r(full["value"]) and line["ms_per_step"] == bench._r(full["ms_per_step"])
 
 
 def test_every_headline_algo_has_a_workload_label():
