@@ -64,6 +64,11 @@ typedef struct sas_index sas_index;
 #define SAS_RANGE_NO_INLINE (1u << 27) /* sas_search_range(_fixed): on a two/four-suffix inline
                                         prefix table, bisect both bounds from the table's rank
                                         range instead of testing the inline slots first     */
+#define SAS_LOCATE_U32    (1u << 29) /* sas_locate*: out_pos holds u32 positions instead of u64
+                                        (EINVAL for a text of n >= 2^32 chars)              */
+#define SAS_LOCATE_NO_PARTITION (1u << 30) /* sas_locate*, sas_locate_fill: no partition pre-pass; each
+                                        workgroup bisects out_off for its tiles' first queries
+                                        itself (the same result; an A/B hook)               */
 #define SAS_PREFIX_RANGE  (1u << 24) /* search, PLAIN / LCP: start binary_search from the
                                         prefix table's range of q's first p chars, as the
                                         reference's binary_search does (sas/sa_search.rs:
@@ -436,6 +441,41 @@ int sas_search_range_fixed(const sas_index* index, const uint8_t* qbytes, uint32
 /* Copy SA[start .. start+count) (global ranks) out: the text positions of a range. */
 int sas_copy_sa_range(const sas_index* index, uint64_t start, uint64_t count, uint32_t* dst,
                       uint32_t flags);
+
+/* Batched locate: every occurrence position of every query, in CSR form.  out_off[0..nq]
+ * (u64) are the offsets, out_off[nq] the total; the positions of query k are
+ * out_pos[out_off[k] .. out_off[k+1]) in SA rank order (the order of search_prefix), as u64,
+ * or as u32 with SAS_LOCATE_U32.  Every SA storage is served: u32, packed 40-bit, tagged
+ * entries and SAS_BUILD_TAG_LINES (there each rank costs a binary search over the buckets'
+ * first ranks: correct, not tuned).
+ *
+ * sas_locate_offsets (device pointers only, asynchronous on `stream`):
+ *   cnt[k] = ranks in both [lo[k], hi[k]) and [rank_lo, rank_lo + sa_entries) (hi < lo: none), capped at
+ *   max_per_query unless that is 0; out_off = exclusive scan of cnt.  A shard or part counts
+ *   only the ranks it holds, so the union over shards is the whole answer; the reference's
+ *   search_range(Range<&Seq>) is lo = range(a).lo, hi = range(b).lo.
+ * sas_locate_fill (device pointers only, asynchronous, no host synchronisation):
+ *   out_pos[out_off[k] + j] = SA[max(lo[k], rank_lo) + j] for j < out_off[k+1] - out_off[k]
+ *   and out_off[k] + j < capacity; nothing at or past `capacity` is written.  The grid is
+ *   sized from `capacity` (the host never reads the total): the caller checks
+ *   out_off[nq] <= capacity afterwards, the contract of sas_route_pack_cap.  lo / out_off are
+ *   those given to / written by sas_locate_offsets on the same index.
+ * sas_locate / sas_locate_fixed: sas_search_range(_fixed) (same index requirements, same
+ *   query validation), then offsets, then fill.  With SAS_DEVICE_PTRS: asynchronous, scratch
+ *   from the index's stream-ordered pool, out_total (device, may be NULL) = out_off[nq].
+ *   With host pointers: synchronous; *out_total is always set and out_off always filled; if
+ *   the total exceeds `capacity` nothing is copied to out_pos and the call returns ENOSPC
+ *   (out_pos == NULL, capacity == 0 is the sizing call). */
+int sas_locate_offsets(const sas_index* index, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
+                       uint64_t max_per_query, uint64_t* out_off, void* stream, uint32_t flags);
+int sas_locate_fill(const sas_index* index, const uint64_t* lo, const uint64_t* out_off, uint64_t nq,
+                    void* out_pos, uint64_t capacity, void* stream, uint32_t flags);
+int sas_locate(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+               uint64_t nq, uint64_t max_per_query, uint64_t* out_off, void* out_pos, uint64_t capacity,
+               uint64_t* out_total, void* stream, uint32_t flags);
+int sas_locate_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq,
+                     uint64_t max_per_query, uint64_t* out_off, void* out_pos, uint64_t capacity,
+                     uint64_t* out_total, void* stream, uint32_t flags);
 
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself

@@ -8,6 +8,7 @@
  *   sas::interpolation_search<16>(sa,q,cnt) interpolation_search<K>   sas/sa_search.rs:376-421
  *   sas::bench / sas::bench_batch         bench / bench_batch         sas/sa_search.rs:423-451
  *   SaNaive::search / search_prefix       Search::search/_prefix      sas/util.rs:29-47
+ *   SaNaive::locate / search_between      search_prefix for a whole batch (CSR) / Search::search_range(Range)
  *   sas::random_string / random_queries   util.rs:9-26 (ChaCha8Rng::seed_from_u64(31415), main.rs:38)
  *   sas::read_fasta_file                  util.rs:144-169
  *   sst::SortedVec / Eytzinger / STree16 / STree15 / PartitionedSTree16M / DirectMap /
@@ -28,6 +29,7 @@
 #define SAS_HPP
 
 #include <array>
+#include <cerrno>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -192,6 +194,50 @@ class SaNaive {
         const auto r = search_range(q);
         std::vector<uint64_t> v(r.second - r.first);
         if (!v.empty()) check(sas_copy_sa64(h_, r.first, v.size(), v.data(), 0));
+        return std::vector<size_t>(v.begin(), v.end());
+    }
+
+    /* CSR result of locate: query k's positions are pos[off[k] .. off[k+1]), in SA order */
+    struct Located {
+        std::vector<uint64_t> off, pos;
+    };
+
+    /* search_prefix for any number of queries in one call (sas_locate: range search, offsets
+     * and the ragged expansion on the GPU, one copy back); max_per_query caps each query's
+     * positions (0: no cap) */
+    Located locate(const std::vector<Seq>& qs, uint64_t max_per_query = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Located r;
+        r.off.assign(qs.size() + 1, 0);
+        uint64_t total = 0;
+        /* the sizing call (ENOSPC unless nothing occurs), then the real one */
+        const int rc = sas_locate(h_, bytes.data(), qoff.data(), len.data(), qs.size(), max_per_query, r.off.data(),
+                                  nullptr, 0, &total, nullptr, 0);
+        if (rc != ENOSPC) check(rc);
+        r.pos.resize(total);
+        if (total)
+            check(sas_locate(h_, bytes.data(), qoff.data(), len.data(), qs.size(), max_per_query, r.off.data(),
+                             r.pos.data(), total, &total, nullptr, 0));
+        return r;
+    }
+
+    /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
+     * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
+     * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are
+     * sas_locate_offsets + sas_locate_fill, which take device pointers */
+    std::vector<size_t> search_between(Seq a, Seq b) const {
+        const auto r = search_ranges({a, b});
+        const uint64_t lo = r[0].first, hi = r[1].first;
+        std::vector<uint64_t> v(hi > lo ? hi - lo : 0);
+        if (!v.empty()) check(sas_copy_sa64(h_, lo, v.size(), v.data(), 0));
         return std::vector<size_t>(v.begin(), v.end());
     }
 

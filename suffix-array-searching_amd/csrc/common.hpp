@@ -203,6 +203,10 @@ struct sas_index {
     mutable hipMemPool_t route_pool = nullptr;  // stream-ordered scratch of sas_route_pack (first use)
 };
 
+// The index's stream-ordered scratch pool (created on first use, destroyed by sas_free):
+// sas_route_pack and the sas_locate calls allocate from it (sas_search.hip)
+int sas_scratch_pool(const sas_index* x, hipMemPool_t* out);
+
 struct sst_index {
     int layout = 0;
     uint32_t flags = 0;
@@ -253,6 +257,24 @@ __device__ __forceinline__ uint64_t tl_slot(const uint64_t* __restrict__ lines, 
     const uint16_t* h = reinterpret_cast<const uint16_t*>(lines + b * 16);
     const uint32_t* l = reinterpret_cast<const uint32_t*>(lines + b * 16);
     return ((uint64_t)h[4 + j] << 32) | l[12 + j];
+}
+// SAS_BUILD_TAG_LINES: SA[r] (r a local rank) from the line of r's bucket (the last bucket
+// whose first rank is <= r: a binary search over the first-rank table of `keys` buckets), its
+// slot or its overflow entry.  Correct, not tuned: ~2 log4(keys) dependent reads per rank
+// (sas_copy_sa64 and sas_locate_fill on a bucket-line index)
+__device__ __forceinline__ uint64_t tl_sa_at(const uint64_t* __restrict__ lines, const uint64_t* __restrict__ ovf,
+                                             const uint64_t* __restrict__ first, uint64_t keys, uint32_t sb,
+                                             uint64_t r) {
+    uint64_t lo = 0, hi = keys;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (first[mid] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    const uint64_t b = lo - 1, j = r - first[b];
+    const uint64_t e = j < SAS_TL_SLOTS ? tl_slot(lines, b, (uint32_t)j)
+                                        : ovf[(lines[b * 16] & (SAS_SA40_MAX - 1)) + j - SAS_TL_SLOTS];
+    return e & tl_sa_mask(sb);
 }
 template <int W>
 struct SaView {

@@ -1923,19 +1923,7 @@ __global__ void k_widen_sa(SaView<W> sa, uint64_t start, uint64_t count, uint64_
 __global__ void k_tl_sa(const uint64_t* __restrict__ lines, const uint64_t* __restrict__ ovf,
                         const uint64_t* __restrict__ first, uint64_t keys, uint32_t sb, uint64_t start, uint64_t count,
                         uint64_t* __restrict__ out) {
-    GRID_STRIDE(i, count) {
-        const uint64_t r = start + i;
-        uint64_t lo = 0, hi = keys;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (first[mid] > r) hi = mid;
-            else lo = mid + 1;
-        }
-        const uint64_t b = lo - 1, j = r - first[b];
-        const uint64_t e = j < SAS_TL_SLOTS ? tl_slot(lines, b, (uint32_t)j)
-                                            : ovf[(lines[b * 16] & (SAS_SA40_MAX - 1)) + j - SAS_TL_SLOTS];
-        out[i] = e & tl_sa_mask(sb);
-    }
+    GRID_STRIDE(i, count) out[i] = tl_sa_at(lines, ovf, first, keys, sb, start + i);
 }
 
 extern "C" int sas_copy_sa64(const sas_index* index, uint64_t start, uint64_t count, uint64_t* dst, uint32_t flags) {

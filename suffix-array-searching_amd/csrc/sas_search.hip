@@ -4176,7 +4176,7 @@ __global__ void k_pack_totals(const uint64_t* __restrict__ base_slot, uint32_t W
 // owned by the index (created on first use, destroyed by sas_free).  Its release threshold
 // of "never" keeps freed blocks for the next step; the device's default pool, which other
 // libraries in the process share, is left alone.
-static int route_pool(const sas_index* x, hipMemPool_t* out) {
+int sas_scratch_pool(const sas_index* x, hipMemPool_t* out) {
     static std::mutex mu;
     std::lock_guard<std::mutex> g(mu);
     if (!x->route_pool) {
@@ -4238,7 +4238,7 @@ static int route_pack_impl(const sas_index* x, const uint64_t* splitter_pos, uin
         return 0;
     }
     hipMemPool_t pool;
-    TRY_RC(route_pool(x, &pool));
+    TRY_RC(sas_scratch_pool(x, &pool));
     // with splitters the routing reads each query anyway and packs it on the way (words);
     // without (one part) the routing reads nothing and the scatter packs from the bytes
     const bool pack_in_route = packed && nsplit > 0;

@@ -26,6 +26,8 @@ SAS_PREFIX_RANGE = 1 << 24
 SAS_NO_PREFIX_TABLE = 1 << 25
 SAS_RANGE_NO_INLINE = 1 << 27
 SAS_QUERIES_ARE_SLICES = 1 << 28
+SAS_LOCATE_U32 = 1 << 29
+SAS_LOCATE_NO_PARTITION = 1 << 30
 SAS_ROUTE_PACKED = 1 << 26
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
@@ -160,6 +162,10 @@ def lib():
     L.sas_search_range.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u32]
     L.sas_search_range_fixed.argtypes = [vp, vp, u32, u64, vp, vp, vp, u32]
     L.sas_copy_sa_range.argtypes = [vp, u64, u64, vp, u32]
+    L.sas_locate_offsets.argtypes = [vp, vp, vp, u64, u64, vp, vp, u32]
+    L.sas_locate_fill.argtypes = [vp, vp, vp, u64, vp, u64, vp, u32]
+    L.sas_locate.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, u32]
+    L.sas_locate_fixed.argtypes = [vp, vp, u32, u64, u64, vp, vp, u64, vp, vp, u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

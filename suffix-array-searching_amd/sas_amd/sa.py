@@ -13,6 +13,7 @@ of suffix comparisons the query made.
 from __future__ import annotations
 
 import ctypes as C
+import errno
 from dataclasses import dataclass
 
 import numpy as np
@@ -93,6 +94,13 @@ class SaNaive:
         self.sa_n = self.stats()["sa_entries"]  # SA entries held (n, or a shard's rank range)
         self.rank_lo = self.stats()["rank_lo"]
         self.next_pos = self.stats()["next_pos"]  # SA value of the rank after this index's range
+        self._device = None  # the GPU the index was built on (the current one at build time)
+        try:
+            import torch
+            if torch.cuda.is_available():
+                self._device = torch.cuda.current_device()
+        except ImportError:
+            pass
 
     @classmethod
     def build(cls, t, sa=None, lcp: bool = True, stree: bool | None = None, verify: bool = False,
@@ -526,6 +534,123 @@ class SaNaive:
         out = np.zeros(max(cnt, 1), np.uint32)
         check(lib().sas_copy_sa_range(self._h, int(lo[0]), cnt, out.ctypes.data, 0))
         return out[:cnt]
+
+    # -- batched locate: every occurrence position of every query (sas_locate*)
+    def locate_ranges(self, lo, hi, max_per_query: int = 0, out=None, capacity: int | None = None,
+                      u32: bool = False, stream=None, flags: int = 0):
+        """Positions of the SA rank ranges [lo[k], hi[k]) this index holds, in CSR form
+        (sas_locate_offsets + sas_locate_fill): torch CUDA int64 lo / hi in -> (off, pos), off
+        int64 [nq + 1], query k's positions pos[off[k] : off[k + 1]] in SA rank order (int64, or
+        with u32 int32 holding the u32 bit patterns).  max_per_query caps each query's count
+        (0: no cap).  Without out / capacity the total is read back once (off[nq].item()) to
+        size pos; with `out` (a tensor to fill) or `capacity` nothing synchronises, pos is the
+        whole buffer, nothing at or past its capacity is written and the caller checks
+        off[nq] <= capacity.  A shard emits only the ranks it holds."""
+        import torch
+        if not (_is_cuda(lo) and _is_cuda(hi)) or lo.dtype != torch.int64 or hi.dtype != torch.int64 or \
+                lo.numel() != hi.numel() or not lo.is_contiguous() or not hi.is_contiguous():
+            raise ValueError("locate_ranges: contiguous torch CUDA int64 lo and hi of the same length")
+        nq = int(lo.numel())
+        dt = torch.int32 if u32 else torch.int64
+        fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+        st = stream if stream is not None else torch.cuda.current_stream(lo.device).cuda_stream
+        off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
+        check(lib().sas_locate_offsets(self._h, _ptr(lo), _ptr(hi), nq, int(max_per_query), _ptr(off), st,
+                                       _lib.SAS_DEVICE_PTRS))
+        total = None
+        if out is None:
+            if capacity is None:
+                capacity = total = int(off[nq].item())
+            out = torch.empty(max(int(capacity), 1), dtype=dt, device=lo.device)
+        else:
+            if not _is_cuda(out) or out.dtype != dt or not out.is_contiguous():
+                raise ValueError(f"locate_ranges: out must be a contiguous CUDA {dt} tensor")
+            capacity = out.numel() if capacity is None else capacity
+            if capacity > out.numel():
+                raise ValueError("locate_ranges: capacity exceeds out")
+        check(lib().sas_locate_fill(self._h, _ptr(lo), _ptr(off), nq, _ptr(out), int(capacity), st, fl))
+        return off, (out[:total] if total is not None else out)
+
+    def _locate(self, qbytes, qoff, qlen, m, nq, max_per_query, u32, stream, out, capacity, flags):
+        if _is_cuda(qbytes):
+            import torch
+            if out is None and capacity is None:  # ranges, offsets, one read of the total, fill
+                lo, hi = (self.search_range(qbytes, qoff, qlen, stream=stream, flags=flags) if qoff is not None
+                          else self.search_range_fixed(qbytes, m, stream=stream, flags=flags))
+                return self.locate_ranges(lo, hi, max_per_query, u32=u32, stream=stream,
+                                          flags=flags & _lib.SAS_LOCATE_NO_PARTITION)
+            dt = torch.int32 if u32 else torch.int64
+            if out is None:
+                out = torch.empty(max(int(capacity), 1), dtype=dt, device=qbytes.device)
+            elif not _is_cuda(out) or out.dtype != dt or not out.is_contiguous():
+                raise ValueError(f"locate: out must be a contiguous CUDA {dt} tensor")
+            capacity = out.numel() if capacity is None else capacity
+            if capacity > out.numel():
+                raise ValueError("locate: capacity exceeds out")
+            off = torch.empty(nq + 1, dtype=torch.int64, device=qbytes.device)
+            st = stream if stream is not None else torch.cuda.current_stream(qbytes.device).cuda_stream
+            fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+            if qoff is not None:
+                rc = lib().sas_locate(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, int(max_per_query),
+                                      _ptr(off), _ptr(out), int(capacity), None, st, fl)
+            else:
+                rc = lib().sas_locate_fixed(self._h, _ptr(qbytes), m, nq, int(max_per_query), _ptr(off), _ptr(out),
+                                            int(capacity), None, st, fl)
+            check(rc)
+            return off, out
+        qbytes = _as_u8(qbytes)
+        fl = flags | (_lib.SAS_LOCATE_U32 if u32 else 0)
+        off = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+
+        def call(pos, cap):
+            if qoff is not None:
+                return lib().sas_locate(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, int(max_per_query),
+                                        _ptr(off), _ptr(pos), cap, C.byref(total), stream, fl)
+            return lib().sas_locate_fixed(self._h, _ptr(qbytes), m, nq, int(max_per_query), _ptr(off), _ptr(pos),
+                                          cap, C.byref(total), stream, fl)
+
+        rc = call(None, 0)  # the sizing call: ENOSPC unless nothing occurs
+        if rc not in (0, errno.ENOSPC):
+            check(rc)
+        pos = np.zeros(max(total.value, 1), np.uint32 if u32 else np.uint64)
+        if total.value:
+            check(call(pos, total.value))
+        return off, pos[:total.value]
+
+    def locate(self, qbytes, qoff, qlen, max_per_query: int = 0, u32: bool = False, stream=None, out=None,
+               capacity: int | None = None, flags: int = 0):
+        """Every occurrence position of every ragged query qbytes[qoff[k] : qoff[k] + qlen[k]]
+        in one call (sas_locate): (off, pos) in CSR form as locate_ranges gives them.  numpy in
+        -> numpy out (a sizing call, then the real one); torch CUDA in -> CUDA out, async when
+        out / capacity is given (otherwise the total is read back once)."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._locate(qbytes, qoff, qlen, 0, nq, max_per_query, u32, stream, out, capacity, flags)
+
+    def locate_fixed(self, qbytes, m: int, max_per_query: int = 0, u32: bool = False, stream=None, out=None,
+                     capacity: int | None = None, flags: int = 0):
+        """locate for fixed-length queries qbytes[k*m : (k+1)*m] (sas_locate_fixed)."""
+        if m <= 0:
+            raise ValueError("use locate for empty queries")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._locate(qbytes, None, None, m, nq, max_per_query, u32, stream, out, capacity, flags)
+
+    def locate_between(self, a, b) -> np.ndarray:
+        """Positions of the suffixes s with a <= s < b, in SA order (Search::search_range over a
+        Range<&Seq>, sas/util.rs:41-46): the ranks from range(a).lo to range(b).lo."""
+        import torch
+        a, b = _as_u8(a), _as_u8(b)
+        buf = np.concatenate([a, b, np.zeros(64, np.uint8)])
+        lo, _ = self.search_range(buf, np.array([0, len(a)], np.uint64), np.array([len(a), len(b)], np.uint32))
+        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+        dlo = torch.tensor([int(lo[0])], dtype=torch.int64, device=dev)
+        dhi = torch.tensor([int(lo[1])], dtype=torch.int64, device=dev)
+        _, pos = self.locate_ranges(dlo, dhi)
+        return pos.cpu().numpy().astype(np.uint64)
 
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
