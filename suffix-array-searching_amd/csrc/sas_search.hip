@@ -1859,7 +1859,9 @@ __global__ __launch_bounds__(SEARCH_BLOCK, 8) void k_sa_inline(SearchArgs a) {
 #define SAS_PREFIX_NT_OUT 0  // non-temporal position stores (k_sa_prefix2)
 #endif
 #ifndef SAS_PREFIX_QWMAX
-#define SAS_PREFIX_QWMAX 8  // register-resident query words (later ones repacked from the bytes)
+// most query words k_sa_prefix holds in registers: 8, or 4 with the later words of a longer
+// query repacked from the bytes (QueryRegs repacks only at QW > 2: the static_assert above launch_table)
+#define SAS_PREFIX_QWMAX 8
 #endif
 // k_sa_prefix2 on the headline shape (fixed 32-char queries, lane pairs): queries in flight
 // per lane pair (round 6 A/B hook; 1 = one lookup at a time)
@@ -2167,16 +2169,6 @@ __global__ __launch_bounds__(SEARCH_BLOCK, 8) void k_sa_prefix_range(SearchArgs 
     if (bad) atomicOr(a.bad, 1u);
 }
 
-template <bool KO, int W>
-static void launch_prefix_range(int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a, uint64_t* dhi) {
-    switch (qw) {
-        case 1: hipLaunchKernelGGL((k_sa_prefix_range<1, KO, W>), grid, block, 0, st, a, dhi); break;
-        case 2: hipLaunchKernelGGL((k_sa_prefix_range<2, KO, W>), grid, block, 0, st, a, dhi); break;
-        case 4: hipLaunchKernelGGL((k_sa_prefix_range<4, KO, W>), grid, block, 0, st, a, dhi); break;
-        default: hipLaunchKernelGGL((k_sa_prefix_range<8, KO, W>), grid, block, 0, st, a, dhi); break;
-    }
-}
-
 // Occurrence ranges on a G-slot inline prefix table (SAS_BUILD_PREFIX_INLINE2 / _INLINE4):
 // the G lanes of a query read its entry (the first G suffixes of the range of its p-char
 // key) as one request and test both bounds' predicates on every slot: lo = the first slot
@@ -2258,23 +2250,6 @@ __global__ __launch_bounds__(SEARCH_BLOCK, 8) void k_sa_prefix2_range(SearchArgs
         }
     }
     if (bad) atomicOr(a.bad, 1u);
-}
-
-template <int G, bool HI40>
-static void launch_prefix2_range_h(int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a,
-                                   uint64_t* dhi) {
-    switch (qw) {
-        case 1: hipLaunchKernelGGL((k_sa_prefix2_range<1, G, HI40>), grid, block, 0, st, a, dhi); break;
-        case 2: hipLaunchKernelGGL((k_sa_prefix2_range<2, G, HI40>), grid, block, 0, st, a, dhi); break;
-        case 4: hipLaunchKernelGGL((k_sa_prefix2_range<4, G, HI40>), grid, block, 0, st, a, dhi); break;
-        default: hipLaunchKernelGGL((k_sa_prefix2_range<8, G, HI40>), grid, block, 0, st, a, dhi); break;
-    }
-}
-
-template <int G>
-static void launch_prefix2_range(int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a, uint64_t* dhi) {
-    if (a.prefix_hi40) launch_prefix2_range_h<G, true>(qw, grid, block, st, a, dhi);
-    else launch_prefix2_range_h<G, false>(qw, grid, block, st, a, dhi);
 }
 
 // ------------------------------------------------------------------ INTERP
@@ -3020,245 +2995,317 @@ __global__ void k_validate_queries(const uint8_t* __restrict__ qb, const uint64_
     if (b & 0xFCu) atomicOr(bad, 1u);
 }
 
-// ------------------------------------------------------------------ host dispatch
-template <int W>
-static void launch_w(int algo, bool top, bool range, int qw, dim3 grid, dim3 block, hipStream_t st,
-                     const SearchArgs& a) {
-#define QW_CASE(KERNEL_T)                                                           \
-    switch (qw) {                                                                   \
-        case 1: hipLaunchKernelGGL(KERNEL_T(1), grid, block, 0, st, a); break;      \
-        case 2: hipLaunchKernelGGL(KERNEL_T(2), grid, block, 0, st, a); break;      \
-        case 4: hipLaunchKernelGGL(KERNEL_T(4), grid, block, 0, st, a); break;      \
-        default: hipLaunchKernelGGL(KERNEL_T(8), grid, block, 0, st, a); break;     \
-    }
-    // the query words all in registers when the batch's longest query is known to fit them
-    const bool exq = a.m_max && a.m_max <= 32u * (uint32_t)qw && qw <= 8;
-#define QWX_CASE(KERNEL_T)                                                                      \
-    switch (qw) {                                                                               \
-        case 1: hipLaunchKernelGGL(KERNEL_T(1, false), grid, block, 0, st, a); break;           \
-        case 2: hipLaunchKernelGGL(KERNEL_T(2, false), grid, block, 0, st, a); break;           \
-        case 4:                                                                                 \
-            if (exq) hipLaunchKernelGGL(KERNEL_T(4, true), grid, block, 0, st, a);              \
-            else hipLaunchKernelGGL(KERNEL_T(4, false), grid, block, 0, st, a);                 \
-            break;                                                                              \
-        default:                                                                                \
-            if (exq) hipLaunchKernelGGL(KERNEL_T(8, true), grid, block, 0, st, a);              \
-            else hipLaunchKernelGGL(KERNEL_T(8, false), grid, block, 0, st, a);                 \
-            break;                                                                              \
-    }
-#define K_PLAIN_TOP(Q, X) (k_sa_binary<Q, BS_PLAIN, true, W, false, X>)
-#define K_PLAIN(Q, X) (k_sa_binary<Q, BS_PLAIN, false, W, false, X>)
-#define K_LCP_TOP(Q, X) (k_sa_binary<Q, BS_MLR, true, W, false, X>)
-#define K_LCP(Q, X) (k_sa_binary<Q, BS_MLR, false, W, false, X>)
-#define K_LLCP_TOP(Q, X) (k_sa_binary<Q, BS_LLCP, true, W, false, X>)
-#define K_LLCP(Q, X) (k_sa_binary<Q, BS_LLCP, false, W, false, X>)
-#define K_PLAIN_RANGE(Q) (k_sa_binary<Q, BS_PLAIN, false, W, true>)
-#define K_LCP_RANGE(Q) (k_sa_binary<Q, BS_MLR, false, W, true>)
-#define K_STREE(Q) (k_sa_stree<Q, W>)
-#define K_STREE4X(Q, X) (k_sa_stree4x<Q, W, false, X>)
-#define K_STREE4X_LT(Q, X) (k_sa_stree4x<Q, W, true, X>)
-#define K_SECTOR(Q) (k_sa_sector<Q>)
-    if (algo == SAS_ALGO_PLAIN && range) {
-        QW_CASE(K_PLAIN_RANGE)
-    } else if (algo == SAS_ALGO_LCP && range) {
-        QW_CASE(K_LCP_RANGE)
-    } else if (algo == SAS_ALGO_PLAIN) {
-        if (top) { QWX_CASE(K_PLAIN_TOP) } else { QWX_CASE(K_PLAIN) }
-    } else if (algo == SAS_ALGO_LCP) {
-        if (top) { QWX_CASE(K_LCP_TOP) } else { QWX_CASE(K_LCP) }
-    } else if (algo == SAS_ALGO_LLCP) {
-        if (top) { QWX_CASE(K_LLCP_TOP) } else { QWX_CASE(K_LLCP) }
-    } else if (algo == SAS_ALGO_STREE) {
-        // m <= 32: the cooperative kernel (descent dominates); longer: one lane per query
-        if (qw == 1 && !SAS_STREE_PERLANE) hipLaunchKernelGGL(K_STREE(1), grid, block, 0, st, a);
-        else { QWX_CASE(K_STREE4X) }
-    } else if (algo == SAS_ALGO_STREE_LLCP) {
-        // the same descent, the LLCP tail (stree_tail) on one lane per query at every m: the
-        // tail's walk to its in-run mids diverges between queries, which a 4-lane group per
-        // query would pay 4 times over (m = 32: 1.77 ms cooperative)
-        QWX_CASE(K_STREE4X_LT)
-    } else {  // SAS_ALGO_SECTOR: positions come from the fused leaves, W = 4 only
-        QW_CASE(K_SECTOR)
-    }
-#undef QW_CASE
-#undef QWX_CASE
+// ------------------------------------------------------------------ launching
+// One host launcher a family.  Those that take a LaunchCtx run SEARCH_BLOCK workgroups sized by
+// launch_search / launch_range; those that take num_cus size their own (their A/B macros).
+struct LaunchCtx { dim3 grid, block; hipStream_t st; };
+
+// Workgroups of bs lanes for `lanes` lanes, at most max_blocks (the kernels stride over the batch)
+inline LaunchCtx launch_ctx(uint64_t lanes, uint64_t bs, uint64_t max_blocks, hipStream_t st) {
+    uint64_t blocks = (lanes + bs - 1) / bs;
+    if (blocks > max_blocks) blocks = max_blocks;
+    return {dim3((unsigned)blocks), dim3((unsigned)bs), st};
 }
 
-// QUAD / INLINE: fused leaves read no SA (W = 4 instantiation only); KO leaves read
-// SA values through SaView<W>.
-template <bool KO, int W>
-static void launch_quad(int algo, bool top, int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a) {
-#define QW_CASE(KERNEL_T)                                                           \
-    switch (qw) {                                                                   \
-        case 1: hipLaunchKernelGGL(KERNEL_T(1), grid, block, 0, st, a); break;      \
-        case 2: hipLaunchKernelGGL(KERNEL_T(2), grid, block, 0, st, a); break;      \
-        case 4: hipLaunchKernelGGL(KERNEL_T(4), grid, block, 0, st, a); break;      \
-        default: hipLaunchKernelGGL(KERNEL_T(8), grid, block, 0, st, a); break;     \
+template <class K, class... A>
+inline void launch(const LaunchCtx& c, K k, A... args) { hipLaunchKernelGGL(k, c.grid, c.block, 0, c.st, args...); }
+
+// The kernels are instantiated per query words held in registers: qw (qw_for: 1, 2, 4, and 8
+// for anything longer) as a compile-time constant, f(std::integral_constant<int, QW>)
+template <class F>
+void with_qw(int qw, F&& f) {
+    switch (qw) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
     }
-#define K_INLINE_TOP(Q) (k_sa_inline<Q, true, KO, W>)
-#define K_INLINE(Q) (k_sa_inline<Q, false, KO, W>)
-#define K_PREFIX(Q) (k_sa_prefix<(Q < SAS_PREFIX_QWMAX ? Q : SAS_PREFIX_QWMAX), KO, W, 4>)
-#define K_PREFIX5(Q) (k_sa_prefix<(Q < SAS_PREFIX_QWMAX ? Q : SAS_PREFIX_QWMAX), KO, W, 5>)
-#define K_PREFIX2(Q) (k_sa_prefix2<Q, 2>)
-#define K_PREFIX4(Q) (k_sa_prefix2<Q, 4>)
-#define K_PREFIX2H(Q) (k_sa_prefix2<Q, 2, true>)
-#define K_PREFIX4H(Q) (k_sa_prefix2<Q, 4, true>)
-#define K_PREFIX16(Q) (k_sa_prefix<(Q < SAS_PREFIX_QWMAX ? Q : SAS_PREFIX_QWMAX), KO, W, 16>)
+}
+
+// The batch's longest query is known and fits the qw register words: no word is ever repacked
+// from the bytes (QueryRegsExact)
+inline bool all_words_in_regs(const SearchArgs& a, int qw) {
+    return a.m_max && a.m_max <= 32u * (uint32_t)qw && qw <= 8;
+}
+
+// with_qw and the register-resident variant, which exists at QW = 4 and 8 only:
+// f(std::integral_constant<int, QW>, std::bool_constant<EXQ>)
+template <class F>
+void with_qw_exq(int qw, bool exq, F&& f) {
+    with_qw(qw, [&](auto Q) {
+        if constexpr (decltype(Q)::value >= 4) {
+            if (exq) return f(Q, std::true_type{});
+        }
+        f(Q, std::false_type{});
+    });
+}
+
+// The index's leaf format as compile-time constants, f(std::bool_constant<KO>,
+// std::integral_constant<int, W>): fused leaves hold their SA values (the W = 4 instances, no
+// SA reads); key-only leaves (SAS_BUILD_QUAD_COMPACT) read them through SaView<W>
+template <class F>
+void with_leaves(bool ko, uint32_t sa_w, F&& f) {
+    if (!ko) f(std::false_type{}, std::integral_constant<int, 4>{});
+    else if (sa_w == 5) f(std::true_type{}, std::integral_constant<int, 5>{});
+    else f(std::true_type{}, std::integral_constant<int, 4>{});
+}
+
+// PLAIN / LCP / LLCP: the query words all in registers when the batch's longest query is known
+// to fit them
+template <int MODE, int W>
+static void launch_mode(const LaunchCtx& c, const SearchArgs& a, int qw, bool top) {
+    with_qw_exq(qw, all_words_in_regs(a, qw), [&](auto Q, auto X) {
+        constexpr int QW = decltype(Q)::value;
+        constexpr bool EXQ = decltype(X)::value;
+        if (top) launch(c, k_sa_binary<QW, MODE, true, W, false, EXQ>, a);
+        else launch(c, k_sa_binary<QW, MODE, false, W, false, EXQ>, a);
+    });
+}
+
+template <int MODE, int W>
+static void launch_mode_range(const LaunchCtx& c, const SearchArgs& a, int qw) {
+    with_qw(qw, [&](auto Q) { launch(c, k_sa_binary<decltype(Q)::value, MODE, false, W, true>, a); });
+}
+
+template <int W>
+static void launch_binary_w(const LaunchCtx& c, const SearchArgs& a, int algo, int qw, bool top, bool range) {
+    // tagged indexes (W = 8) serve PLAIN and LCP from the whole array only
+    if constexpr (W != 8) {
+        if (algo == SAS_ALGO_PLAIN && range) return launch_mode_range<BS_PLAIN, W>(c, a, qw);
+        if (algo == SAS_ALGO_LCP && range) return launch_mode_range<BS_MLR, W>(c, a, qw);
+        if (algo == SAS_ALGO_LLCP) return launch_mode<BS_LLCP, W>(c, a, qw, top);
+    }
+    if (algo == SAS_ALGO_PLAIN) launch_mode<BS_PLAIN, W>(c, a, qw, top);
+    else launch_mode<BS_MLR, W>(c, a, qw, top);
+}
+
+static void launch_binary(int num_cus, hipStream_t st, const SearchArgs& a, int algo, uint32_t sa_w, int qw, bool top,
+                          bool range) {
+    // k_sa_binary instances: QW = qw (1, 2, 4, and 8 for anything longer), one lane per query
+    const LaunchCtx c = launch_ctx(a.nq, BIN_BLOCK(qw), (uint64_t)num_cus * SAS_BIN_BPC, st);
+    if (sa_w == 8) launch_binary_w<8>(c, a, algo, qw, top, range);
+    else if (sa_w == 5) launch_binary_w<5>(c, a, algo, qw, top, range);
+    else launch_binary_w<4>(c, a, algo, qw, top, range);
+}
+
+// STREE / STREE_LLCP
+template <int W>
+static void launch_stree_w(int num_cus, hipStream_t st, const SearchArgs& a, int algo, int qw) {
+    const uint64_t cap = (uint64_t)num_cus * SAS_BIN_BPC;
+    // m <= 32: the cooperative kernel (descent dominates); longer: one lane per query
+    if (algo == SAS_ALGO_STREE && qw == 1 && !SAS_STREE_PERLANE)
+        return launch(launch_ctx(a.nq * QUAD_G, SAS_BIN_BLOCK, cap, st), k_sa_stree<1, W>, a);
+    const LaunchCtx c = launch_ctx(a.nq, BIN_BLOCK(qw), cap, st);
+    with_qw_exq(qw, all_words_in_regs(a, qw), [&](auto Q, auto X) {
+        constexpr int QW = decltype(Q)::value;
+        constexpr bool EXQ = decltype(X)::value;
+        // STREE_LLCP: the same descent, the LLCP tail (stree_tail) on one lane per query at every
+        // m: the tail's walk to its in-run mids diverges between queries, which a 4-lane group
+        // per query would pay 4 times over (m = 32: 1.77 ms cooperative)
+        if (algo == SAS_ALGO_STREE) launch(c, k_sa_stree4x<QW, W, false, EXQ>, a);
+        else launch(c, k_sa_stree4x<QW, W, true, EXQ>, a);
+    });
+}
+
+static void launch_stree(int num_cus, hipStream_t st, const SearchArgs& a, int algo, uint32_t sa_w, int qw) {
+    if (sa_w == 5) launch_stree_w<5>(num_cus, st, a, algo, qw);
+    else launch_stree_w<4>(num_cus, st, a, algo, qw);
+}
+
+// SECTOR: positions come from the fused leaves, no SA reads, one instance per QW
+static void launch_sector(const LaunchCtx& c, const SearchArgs& a, int qw) {
+    with_qw(qw, [&](auto Q) { launch(c, k_sa_sector<decltype(Q)::value>, a); });
+}
+
+static void launch_sector_range(const LaunchCtx& c, const SearchArgs& a, int qw, uint64_t* dhi) {
+    with_qw(qw, [&](auto Q) { launch(c, k_sa_sector_range<decltype(Q)::value>, a, dhi); });
+}
+
+// QUAD / INLINE
+template <bool KO, int W>
+static void launch_quad_leaves(const LaunchCtx& c, const SearchArgs& a, int algo, int qw, bool top) {
     if (algo == SAS_ALGO_QUAD) {
         // m <= 32: the cooperative kernel; longer: one lane per query (as STREE), two query
         // words in registers (m <= 64), later ones repacked from the bytes
-        if (qw == 1) hipLaunchKernelGGL((k_sa_quad<1, KO, W>), grid, block, 0, st, a);
-        else if (qw == 2) hipLaunchKernelGGL((k_sa_quad4x<2, KO, W, false>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_sa_quad4x<SAS_QUAD4X_MAXREGS, KO, W, true>), grid, block, 0, st, a);
-    } else if (algo == SAS_ALGO_PREFIX) {
-        if (a.prefix_w == 5) { QW_CASE(K_PREFIX5) }
-        else if (a.prefix_w == 16 && !KO) { QW_CASE(K_PREFIX16) }
-        else if (a.prefix_w == 32 && !KO && a.prefix_hi40) { QW_CASE(K_PREFIX2H) }
-        else if (a.prefix_w == 64 && !KO && a.prefix_hi40) { QW_CASE(K_PREFIX4H) }
-        else if (a.prefix_w == 32 && !KO) { QW_CASE(K_PREFIX2) }
-        else if (a.prefix_w == 64 && !KO) { QW_CASE(K_PREFIX4) }
-        else { QW_CASE(K_PREFIX) }
+        if (qw == 1) launch(c, k_sa_quad<1, KO, W>, a);
+        else if (qw == 2) launch(c, k_sa_quad4x<2, KO, W, false>, a);
+        else launch(c, k_sa_quad4x<SAS_QUAD4X_MAXREGS, KO, W, true>, a);
+    } else if (top) {
+        with_qw(qw, [&](auto Q) { launch(c, k_sa_inline<decltype(Q)::value, true, KO, W>, a); });
     } else {
-        if (top) { QW_CASE(K_INLINE_TOP) } else { QW_CASE(K_INLINE) }
+        with_qw(qw, [&](auto Q) { launch(c, k_sa_inline<decltype(Q)::value, false, KO, W>, a); });
     }
-#undef QW_CASE
 }
 
-// INTERP: fused quad leaves (W = 4 instantiation, no SA reads) or SA + text at any width
+static void launch_quad(const LaunchCtx& c, const SearchArgs& a, int algo, bool ko, uint32_t sa_w, int qw, bool top) {
+    with_leaves(ko, sa_w, [&](auto KO, auto W) {
+        launch_quad_leaves<decltype(KO)::value, decltype(W)::value>(c, a, algo, qw, top);
+    });
+}
+
+static void launch_quad_range(const LaunchCtx& c, const SearchArgs& a, bool ko, uint32_t sa_w, int qw, uint64_t* dhi) {
+    with_leaves(ko, sa_w, [&](auto KO, auto W) {
+        with_qw(qw, [&](auto Q) {
+            launch(c, k_sa_quad_range<decltype(Q)::value, decltype(KO)::value, decltype(W)::value>, a, dhi);
+        });
+    });
+}
+
+// QUAD_LLCP past 32 chars.  Fused leaves, any SA width (the leaves and the LLCP entries carry
+// 40-bit positions), with every query word in registers when the batch's longest query is known
+// to fit them, else two words and the rest repacked from the bytes.  qw = 1 goes to QUAD
+// (launch_search).
+static void launch_quad_llcp(int num_cus, hipStream_t st, const SearchArgs& a, int qw) {
+    const bool exact = all_words_in_regs(a, qw);
+    const bool r32 = a.sa_n < (1ull << 32);
+    // the grid is sized by QLLCP_BLOCK(2) whatever the workgroup size (the kernels stride over
+    // the batch): launch_ctx with the final block size would change the grid
+    LaunchCtx c = launch_ctx(a.nq, QLLCP_BLOCK(2), (uint64_t)num_cus * 2, st);
+    c.block = dim3((unsigned)(exact ? QLLCP_BLOCK(qw) : QLLCP_BLOCK(2)));
+    auto go = [&](auto Q, auto X) {
+        constexpr int QW = decltype(Q)::value;
+        constexpr bool EXACT = decltype(X)::value;
+        if (r32) launch(c, k_sa_quad_llcp<QW, EXACT, true>, a);
+        else launch(c, k_sa_quad_llcp<QW, EXACT, false>, a);
+    };
+    if (!exact) return go(std::integral_constant<int, 2>{}, std::false_type{});
+    with_qw(qw, [&](auto Q) {
+        if constexpr (decltype(Q)::value >= 2) go(Q, std::true_type{});
+    });
+}
+
+// PREFIX.  QueryRegs<QW>::word returns 0 past the register words for QW <= 2 (such kernels only
+// ever see queries that fit them), so a k_sa_prefix clamped below 4 words would mis-compare long
+// queries
+static_assert(SAS_PREFIX_QWMAX > 2, "SAS_PREFIX_QWMAX: 4 or 8 (QueryRegs repacks later words only for QW > 2)");
+
+// a table of TW-byte entries (4, 5; 16: one inline slot), one lane per query
+template <bool KO, int W, int TW>
+static void launch_table(const LaunchCtx& c, const SearchArgs& a, int qw) {
+    with_qw(qw, [&](auto Q) {
+        constexpr int QW = decltype(Q)::value < SAS_PREFIX_QWMAX ? decltype(Q)::value : SAS_PREFIX_QWMAX;
+        launch(c, k_sa_prefix<QW, KO, W, TW>, a);
+    });
+}
+
+// G inline slots per entry, G lanes per query
+template <int G>
+static void launch_slots(const LaunchCtx& c, const SearchArgs& a, int qw) {
+    with_qw(qw, [&](auto Q) {
+        if (a.prefix_hi40) launch(c, k_sa_prefix2<decltype(Q)::value, G, true>, a);
+        else launch(c, k_sa_prefix2<decltype(Q)::value, G, false>, a);
+    });
+}
+
+template <bool KO, int W>
+static void launch_prefix_leaves(const LaunchCtx& c, const SearchArgs& a, int qw) {
+    if (a.prefix_w == 5) launch_table<KO, W, 5>(c, a, qw);
+    else if (a.prefix_w == 16 && !KO) launch_table<KO, W, 16>(c, a, qw);
+    else if (a.prefix_w == 32 && !KO) launch_slots<2>(c, a, qw);
+    else if (a.prefix_w == 64 && !KO) launch_slots<4>(c, a, qw);
+    else launch_table<KO, W, 4>(c, a, qw);
+}
+
+static void launch_prefix(const LaunchCtx& c, const SearchArgs& a, bool ko, uint32_t sa_w, int qw) {
+    with_leaves(ko, sa_w, [&](auto KO, auto W) {
+        launch_prefix_leaves<decltype(KO)::value, decltype(W)::value>(c, a, qw);
+    });
+}
+
+template <int G>
+static void launch_slots_range(const LaunchCtx& c, const SearchArgs& a, int qw, uint64_t* dhi) {
+    with_qw(qw, [&](auto Q) {
+        if (a.prefix_hi40) launch(c, k_sa_prefix2_range<decltype(Q)::value, G, true>, a, dhi);
+        else launch(c, k_sa_prefix2_range<decltype(Q)::value, G, false>, a, dhi);
+    });
+}
+
+static void launch_prefix_range(const LaunchCtx& c, const SearchArgs& a, bool inline_slots, bool ko, uint32_t sa_w,
+                                int qw, uint64_t* dhi) {
+    if (inline_slots)
+        return a.prefix_w == 32 ? launch_slots_range<2>(c, a, qw, dhi) : launch_slots_range<4>(c, a, qw, dhi);
+    with_leaves(ko, sa_w, [&](auto KO, auto W) {
+        with_qw(qw, [&](auto Q) {
+            launch(c, k_sa_prefix_range<decltype(Q)::value, decltype(KO)::value, decltype(W)::value>, a, dhi);
+        });
+    });
+}
+
+// INTERP
 template <int W, bool FUSED>
-static void launch_interp(int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a, uint32_t range) {
-    switch (qw) {
-        case 1: hipLaunchKernelGGL((k_sa_interp<1, W, FUSED>), grid, block, 0, st, a, range); break;
-        case 2: hipLaunchKernelGGL((k_sa_interp<2, W, FUSED>), grid, block, 0, st, a, range); break;
-        case 4: hipLaunchKernelGGL((k_sa_interp<4, W, FUSED>), grid, block, 0, st, a, range); break;
-        default: hipLaunchKernelGGL((k_sa_interp<8, W, FUSED>), grid, block, 0, st, a, range); break;
-    }
+static void launch_interp_w(const LaunchCtx& c, const SearchArgs& a, int qw, uint32_t range) {
+    with_qw(qw, [&](auto Q) { launch(c, k_sa_interp<decltype(Q)::value, W, FUSED>, a, range); });
 }
 
-// Tagged indexes (sa_w = 8): TAGGED, and PLAIN / LCP reading the SA values from the entries
-static void launch_w8(int algo, bool top, int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a) {
-#define QW_CASE(KERNEL_T)                                                           \
-    switch (qw) {                                                                   \
-        case 1: hipLaunchKernelGGL(KERNEL_T(1), grid, block, 0, st, a); break;      \
-        case 2: hipLaunchKernelGGL(KERNEL_T(2), grid, block, 0, st, a); break;      \
-        case 4: hipLaunchKernelGGL(KERNEL_T(4), grid, block, 0, st, a); break;      \
-        default: hipLaunchKernelGGL(KERNEL_T(8), grid, block, 0, st, a); break;     \
-    }
-#define K_TAGGED(Q) (k_sa_tagged<Q>)
-    const bool exq = a.m_max && a.m_max <= 32u * (uint32_t)qw && qw <= 8;
-#define QWX_CASE(KERNEL_T)                                                                      \
-    switch (qw) {                                                                               \
-        case 1: hipLaunchKernelGGL(KERNEL_T(1, false), grid, block, 0, st, a); break;           \
-        case 2: hipLaunchKernelGGL(KERNEL_T(2, false), grid, block, 0, st, a); break;           \
-        case 4:                                                                                 \
-            if (exq) hipLaunchKernelGGL(KERNEL_T(4, true), grid, block, 0, st, a);              \
-            else hipLaunchKernelGGL(KERNEL_T(4, false), grid, block, 0, st, a);                 \
-            break;                                                                              \
-        default:                                                                                \
-            if (exq) hipLaunchKernelGGL(KERNEL_T(8, true), grid, block, 0, st, a);              \
-            else hipLaunchKernelGGL(KERNEL_T(8, false), grid, block, 0, st, a);                 \
-            break;                                                                              \
-    }
-#define K8_PLAIN_TOP(Q, X) (k_sa_binary<Q, BS_PLAIN, true, 8, false, X>)
-#define K8_PLAIN(Q, X) (k_sa_binary<Q, BS_PLAIN, false, 8, false, X>)
-#define K8_LCP_TOP(Q, X) (k_sa_binary<Q, BS_MLR, true, 8, false, X>)
-#define K8_LCP(Q, X) (k_sa_binary<Q, BS_MLR, false, 8, false, X>)
-    if (algo == SAS_ALGO_TAGGED) {
-        QW_CASE(K_TAGGED)
-    } else if (algo == SAS_ALGO_PLAIN) {
-        if (top) { QWX_CASE(K8_PLAIN_TOP) } else { QWX_CASE(K8_PLAIN) }
-    } else {
-        if (top) { QWX_CASE(K8_LCP_TOP) } else { QWX_CASE(K8_LCP) }
-    }
-#undef QW_CASE
-#undef QWX_CASE
+// fused quad leaves (W = 4 instantiation, no SA reads) or SA + text at any width
+static void launch_interp(const LaunchCtx& c, const SearchArgs& a, bool fused, uint32_t sa_w, int qw, uint32_t range) {
+    if (fused) launch_interp_w<4, true>(c, a, qw, range);
+    else if (sa_w == 8) launch_interp_w<8, false>(c, a, qw, range);
+    else if (sa_w == 5) launch_interp_w<5, false>(c, a, qw, range);
+    else launch_interp_w<4, false>(c, a, qw, range);
 }
 
+// TAGGED, on entries or bucket lines (a.tag_lines).  slices: the queries are slices of the
+// indexed text (SAS_QUERIES_ARE_SLICES)
+static void launch_tagged(int num_cus, hipStream_t st, const SearchArgs& a, int qw, bool slices) {
+    const bool lines = a.tag_lines != nullptr;
+    const uint64_t per_cu = lines ? SAS_TL_LB : (qw >= SAS_TAG_LB_QW ? SAS_TAG_LB : 8);
+    const LaunchCtx c = launch_ctx(a.nq, SAS_TAG_BLOCK, (uint64_t)num_cus * per_cu, st);
+    with_qw(qw, [&](auto Q) {
+        constexpr int QW = decltype(Q)::value;
+        if (lines && slices) launch(c, k_sa_tagged_lines_slices<QW>, a);
+        else if (lines) launch(c, k_sa_tagged_lines<QW>, a);
+        else if (slices) launch(c, k_sa_tagged_slices<QW>, a);
+        else launch(c, k_sa_tagged<QW>, a);
+    });
+}
+
+static void launch_tagged_range(const LaunchCtx& c, const SearchArgs& a, int qw, uint64_t* dhi) {
+    with_qw(qw, [&](auto Q) {
+        constexpr int QW = decltype(Q)::value;
+        if (a.tag_lines) launch(c, k_sa_tagged_lines_range<QW>, a, dhi);
+        else launch(c, k_sa_tagged_range<QW>, a, dhi);
+    });
+}
+
+static void launch_validate(hipStream_t st, const SearchArgs& a, uint64_t nq) {
+    launch(launch_ctx(nq, 256, 65536, st), k_validate_queries, a.qbytes, a.qoff, a.qlen, a.m_fixed, nq, a.bad);
+}
+
+// ------------------------------------------------------------------ host dispatch
+// Which family serves algo on this index.  PLAIN / LCP / LLCP, the S-tree kernels, TAGGED and
+// QUAD_LLCP past 32 chars have workgroup shapes of their own and size their grids themselves.
 static int launch_search(const sas_index* x, SearchArgs& a, int algo, int qw, uint32_t flags, hipStream_t st) {
+    if (a.nq == 0) return 0;
     // PLAIN, LLCP and INLINE read the pivot levels past the LDS ones from the prefix-relative
     // blocks, which the build makes wherever the array has such levels
-    const bool coop = (algo == SAS_ALGO_QUAD || algo == SAS_ALGO_QUAD_LLCP ||
-                       (algo == SAS_ALGO_STREE && !SAS_STREE_PERLANE)) && qw == 1;
-    // inline prefix tables with G slots: G lanes per query
-    const uint64_t g = (algo == SAS_ALGO_PREFIX && x->prefix_w >= 32) ? x->prefix_w / 16 : 1;
-    const uint64_t lanes = a.nq * (coop ? QUAD_G : g);
-    // k_sa_binary (PLAIN / LCP / LLCP, any SA width) and the S-tree kernels have their own
-    // workgroup shape
-    const bool bin = algo == SAS_ALGO_PLAIN || algo == SAS_ALGO_LCP || algo == SAS_ALGO_LLCP ||
-                     algo == SAS_ALGO_STREE || algo == SAS_ALGO_STREE_LLCP;
-    // k_sa_binary / k_sa_stree4x instances: QW = qw (1, 2, 4, and 8 for anything longer);
-    // QUAD_LLCP past 32 chars sizes its two kernels itself
-    const uint64_t bs = bin ? (coop ? SAS_BIN_BLOCK : BIN_BLOCK(qw)) : SEARCH_BLOCK;
-    uint64_t blocks = (lanes + bs - 1) / bs;
-    uint64_t cap = (uint64_t)x->num_cus * (bin ? SAS_BIN_BPC : BLOCKS_PER_CU);
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) return 0;
-    dim3 grid((unsigned)blocks), block((unsigned)bs);
-    bool top = !(flags & SAS_NO_LDS_TOP);
+    const bool top = !(flags & SAS_NO_LDS_TOP);
     const bool range = (flags & SAS_PREFIX_RANGE) != 0;
+    // the others: a lane per query; 4 lanes for QUAD at m <= 32; G on a G-slot inline prefix table
+    const bool coop = (algo == SAS_ALGO_QUAD || algo == SAS_ALGO_QUAD_LLCP) && qw == 1;
+    const uint64_t g = (algo == SAS_ALGO_PREFIX && x->prefix_w >= 32) ? x->prefix_w / 16 : 1;
+    const LaunchCtx c = launch_ctx(a.nq * (coop ? QUAD_G : g), SEARCH_BLOCK, (uint64_t)x->num_cus * BLOCKS_PER_CU, st);
+    const bool ko = x->quad_compact != 0;
     if (algo == SAS_ALGO_TAGGED) {
-        uint64_t tb = (a.nq + SAS_TAG_BLOCK - 1) / SAS_TAG_BLOCK;
-        const uint64_t tcap = (uint64_t)x->num_cus * (x->tag_lines ? SAS_TL_LB : (qw >= SAS_TAG_LB_QW ? SAS_TAG_LB : 8));
-        if (tb > tcap) tb = tcap;
-        if (x->tag_lines) {
-            const dim3 g((unsigned)tb), b(SAS_TAG_BLOCK);
-            const bool sl = (flags & SAS_QUERIES_ARE_SLICES) != 0;
-#define SAS_TL_LAUNCH(Q)                                                                           \
-    if (sl) hipLaunchKernelGGL(k_sa_tagged_lines_slices<Q>, g, b, 0, st, a);                       \
-    else hipLaunchKernelGGL(k_sa_tagged_lines<Q>, g, b, 0, st, a)
-            switch (qw) {
-                case 1: SAS_TL_LAUNCH(1); break;
-                case 2: SAS_TL_LAUNCH(2); break;
-                case 4: SAS_TL_LAUNCH(4); break;
-                default: SAS_TL_LAUNCH(8); break;
-            }
-#undef SAS_TL_LAUNCH
-        } else if (flags & SAS_QUERIES_ARE_SLICES) {
-            const dim3 g((unsigned)tb), b(SAS_TAG_BLOCK);
-            switch (qw) {
-                case 1: hipLaunchKernelGGL(k_sa_tagged_slices<1>, g, b, 0, st, a); break;
-                case 2: hipLaunchKernelGGL(k_sa_tagged_slices<2>, g, b, 0, st, a); break;
-                case 4: hipLaunchKernelGGL(k_sa_tagged_slices<4>, g, b, 0, st, a); break;
-                default: hipLaunchKernelGGL(k_sa_tagged_slices<8>, g, b, 0, st, a); break;
-            }
-        } else {
-            launch_w8(algo, top, qw, dim3((unsigned)tb), dim3(SAS_TAG_BLOCK), st, a);
-        }
+        launch_tagged(x->num_cus, st, a, qw, (flags & SAS_QUERIES_ARE_SLICES) != 0);
     } else if (algo == SAS_ALGO_INTERP) {
-        if (x->quad_leaves && !x->quad_compact) launch_interp<4, true>(qw, grid, block, st, a, range);
-        else if (x->sa_w == 8) launch_interp<8, false>(qw, grid, block, st, a, range);
-        else if (x->sa_w == 5) launch_interp<5, false>(qw, grid, block, st, a, range);
-        else launch_interp<4, false>(qw, grid, block, st, a, range);
-    } else if (x->sa_w == 8) {
-        launch_w8(algo, top, qw, grid, block, st, a);
+        launch_interp(c, a, x->quad_leaves && !ko, x->sa_w, qw, range);
+    } else if (x->sa_w == 8 || algo == SAS_ALGO_PLAIN || algo == SAS_ALGO_LCP || algo == SAS_ALGO_LLCP) {
+        // a tagged index (sa_w = 8): PLAIN / LCP reading the SA values from the entries
+        launch_binary(x->num_cus, st, a, algo, x->sa_w, qw, top, range);
+    } else if (algo == SAS_ALGO_STREE || algo == SAS_ALGO_STREE_LLCP) {
+        launch_stree(x->num_cus, st, a, algo, x->sa_w, qw);
     } else if (algo == SAS_ALGO_QUAD_LLCP && qw == 1) {
         // m <= 32: QUAD (the 32-char key decides every entry)
-        hipLaunchKernelGGL((k_sa_quad<1, false, 4>), grid, block, 0, st, a);
+        launch_quad(c, a, SAS_ALGO_QUAD, false, 4, qw, top);
     } else if (algo == SAS_ALGO_QUAD_LLCP) {
-        // longer: k_sa_quad_llcp (fused leaves, any SA width: the leaves and the LLCP entries carry
-        // 40-bit positions), with every query word in registers when the batch's longest query
-        // is known to fit them, else two words and the rest repacked from the bytes
-        const bool exact = a.m_max && a.m_max <= 32u * (uint32_t)qw && qw <= 8;
-        const bool r32 = a.sa_n < (1ull << 32);
-        uint64_t gq = (a.nq + QLLCP_BLOCK(2) - 1) / QLLCP_BLOCK(2);
-        if (gq > (uint64_t)x->num_cus * 2) gq = (uint64_t)x->num_cus * 2;
-        const dim3 g1((unsigned)gq), b1((unsigned)(exact ? QLLCP_BLOCK(qw) : QLLCP_BLOCK(2)));
-#define QLLCP_GO(Q, X)                                                                            \
-    if (r32) hipLaunchKernelGGL((k_sa_quad_llcp<Q, X, true>), g1, b1, 0, st, a);                  \
-    else hipLaunchKernelGGL((k_sa_quad_llcp<Q, X, false>), g1, b1, 0, st, a)
-        if (!exact) { QLLCP_GO(2, false); }
-        else if (qw == 2) { QLLCP_GO(2, true); }
-        else if (qw == 4) { QLLCP_GO(4, true); }
-        else { QLLCP_GO(8, true); }
-#undef QLLCP_GO
-    } else if (algo == SAS_ALGO_QUAD || algo == SAS_ALGO_INLINE || algo == SAS_ALGO_PREFIX) {
-        if (!x->quad_compact) launch_quad<false, 4>(algo, top, qw, grid, block, st, a);
-        else if (x->sa_w == 5) launch_quad<true, 5>(algo, top, qw, grid, block, st, a);
-        else launch_quad<true, 4>(algo, top, qw, grid, block, st, a);
-    } else if (x->sa_w == 5 && algo != SAS_ALGO_SECTOR) {
-        launch_w<5>(algo, top, range, qw, grid, block, st, a);
+        launch_quad_llcp(x->num_cus, st, a, qw);
+    } else if (algo == SAS_ALGO_QUAD || algo == SAS_ALGO_INLINE) {
+        launch_quad(c, a, algo, ko, x->sa_w, qw, top);
+    } else if (algo == SAS_ALGO_PREFIX) {
+        launch_prefix(c, a, ko, x->sa_w, qw);
     } else {
-        launch_w<4>(algo, top, range, qw, grid, block, st, a);
+        launch_sector(c, a, qw);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3271,7 +3318,13 @@ static int qw_for(uint64_t maxlen) {
     return 8;
 }
 
-static void fill_args(const sas_index* x, SearchArgs& a) {
+// The index's side of the kernel arguments for a batch of nq queries (m_fixed chars each, or 0:
+// ragged); bad-code flag: the index's write-only sink
+static SearchArgs fill_args(const sas_index* x, uint64_t nq, uint32_t m_fixed) {
+    SearchArgs a{};
+    a.nq = nq;
+    a.m_fixed = m_fixed;
+    a.bad = x->scratch;
     a.tw = x->text_w;
     a.n = x->n;
     a.sa_n = x->sa_n;
@@ -3327,6 +3380,7 @@ static void fill_args(const sas_index* x, SearchArgs& a) {
     a.tag_first = x->tag_first;
     a.tw2 = x->text2 ? x->text2 : x->text_w;
     a.tag_sb = x->tag_sb;
+    return a;
 }
 
 // Algorithm / index / flag compatibility, shared by the search entry points.
@@ -3366,9 +3420,22 @@ struct DeviceBuf {
     ~DeviceBuf() { if (p) (void)hipFree(p); }
 };
 
-// Occurrence-range kernel for the index's structures (defined with the range kernels below)
+// Occurrence-range kernel for the index's structures (a.nq queries; lo to a.out_pos, hi to dhi)
 static void launch_range(const sas_index* x, const SearchArgs& a, int qw, uint32_t flags, hipStream_t st,
-                         uint64_t* dhi);
+                         uint64_t* dhi) {
+    const bool quad = x->quad_leaves != nullptr;
+    const bool ko = x->quad_compact != 0;
+    // the prefix table, when built, replaces the two tree descents (one lane per query;
+    // G lanes per query on a G-slot inline table)
+    const bool ptab = quad && x->prefix && !(flags & SAS_NO_PREFIX_TABLE);
+    const bool pair = ptab && !ko && (x->prefix_w == 32 || x->prefix_w == 64) && !(flags & SAS_RANGE_NO_INLINE);
+    const uint64_t per = (quad && !ptab) ? QUAD_G : (pair ? x->prefix_w / 16 : 1);
+    const LaunchCtx c = launch_ctx(a.nq * per, SEARCH_BLOCK, (uint64_t)x->num_cus * BLOCKS_PER_CU, st);
+    if (x->tag_lines || x->tag_table) launch_tagged_range(c, a, qw, dhi);
+    else if (ptab) launch_prefix_range(c, a, pair, ko, x->sa_w, qw, dhi);
+    else if (quad) launch_quad_range(c, a, ko, x->sa_w, qw, dhi);
+    else launch_sector_range(c, a, qw, dhi);
+}
 
 // ------------------------------------------------------------------ host-pointer pipeline
 void sas_stage_pool_free(StagePool* p) {
@@ -3433,9 +3500,7 @@ static int host_pipeline(const sas_index* x, int mode, const uint8_t* qbytes, co
         auto t1 = clk::now();
         t_wait += std::chrono::duration<double, std::milli>(t1 - t0).count();
         const int po = out_pieces(sl);
-        SearchArgs a{};
-        fill_args(x, a);
-        a.m_fixed = m;
+        SearchArgs a = fill_args(x, 0, m);
         uint64_t k = 0, in_bytes = 0;
         int qw = 1;
         // the new chunk: its extent, and a fill function over `pi` pieces
@@ -3510,14 +3575,10 @@ static int host_pipeline(const sas_index* x, int mode, const uint8_t* qbytes, co
         a.nq = k;
         a.out_pos = sl.d_out;
         a.out_probes = out_probes ? sl.d_pr : nullptr;
-        a.bad = x->scratch;
         if (validate) {
             HIP_TRY(hipMemsetAsync(sl.d_bad, 0, 4, sl.st));
             a.bad = sl.d_bad;
-            uint64_t vb = (k + 255) / 256;
-            if (vb > 65536) vb = 65536;
-            hipLaunchKernelGGL(k_validate_queries, dim3((unsigned)vb), dim3(256), 0, sl.st, a.qbytes, a.qoff, a.qlen,
-                               a.m_fixed, k, a.bad);
+            launch_validate(sl.st, a, k);
         }
         if (out_hi) {
             launch_range(x, a, qw, flags, sl.st, sl.d_out + k);
@@ -3563,8 +3624,117 @@ static int host_pipeline(const sas_index* x, int mode, const uint8_t* qbytes, co
     return 0;
 }
 
-// Host-pointer calls stage through plain hipMalloc + synchronous copies: the
-// stream-ordered allocator + pageable async copies raced on the null stream.
+// Host arrays go through the pinned, chunked pipeline (host_pipeline) unless one query alone
+// exceeds a staging chunk (qlen null: fixed length m_fixed)
+static bool fits_stage(uint32_t m_fixed, const uint32_t* qlen, uint64_t nq) {
+    uint64_t maxlen = m_fixed;
+    for (uint64_t k = 0; qlen && k < nq; k++) maxlen = qlen[k] > maxlen ? qlen[k] : maxlen;
+    return maxlen <= SAS_STAGE_BYTES;
+}
+
+// A direct call: device pointers, or host arrays with a query longer than a staging chunk.
+// Such host arrays stage through plain hipMalloc + synchronous copies: the stream-ordered
+// allocator + pageable async copies raced on the null stream.
+// begin() wires a's query, bad-code and output pointers (dev_out[0] is a.out_pos), sets the
+// batch's query words (qw, a.m_max) and launches the validation.  After the caller's kernels,
+// end() synchronises if anything is read back, copies host outputs out and fails with
+// "<what>: query bytes must be DNA codes 0..3" on an invalid code.
+struct DirectIo {  // the caller's arrays, host or device
+    const uint8_t* qbytes;
+    const uint64_t* qoff;  // null: fixed length a.m_fixed
+    const uint32_t* qlen;
+    int nout;  // position arrays: one for a search, two for a range
+    uint64_t* out[2];
+    uint32_t* probes;
+};
+
+struct DirectCall {
+    DirectIo io{};
+    int qw = 4;
+    bool dev = false, check_bad = false;
+    uint64_t* dev_out[2] = {};
+    DeviceBuf bflag, bqb, bqoff, bqlen, bout[2], bprobes;
+
+    // a.nq and a.m_fixed are set
+    int begin(const sas_index* x, hipStream_t st, uint32_t flags, SearchArgs& a, const DirectIo& caller) {
+        io = caller;
+        dev = (flags & SAS_DEVICE_PTRS) != 0;
+        const bool ragged = io.qoff != nullptr;
+        const uint8_t* qbytes = io.qbytes;
+        const uint64_t* qoff = io.qoff;
+        const uint32_t* qlen = io.qlen;
+        const uint64_t nq = a.nq;
+        // invalid-code flag: a per-call word when it is read back, so that concurrent calls
+        // on other streams (allowed: the index is immutable) never see each other's flags;
+        // otherwise the index's write-only sink (fill_args)
+        check_bad = !dev || (flags & SAS_VALIDATE);
+        if (check_bad) {
+            HIP_TRY(hipMalloc(&bflag.p, 4));
+            HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
+            a.bad = static_cast<uint32_t*>(bflag.p);
+        }
+        if (dev) {  // ragged: the longest query is unknown
+            qw = ragged ? 4 : qw_for(a.m_fixed);
+            a.m_max = ragged ? 0 : a.m_fixed;
+            a.qbytes = qbytes;
+            a.qoff = qoff;
+            a.qlen = qlen;
+            dev_out[0] = io.out[0];
+            dev_out[1] = io.out[1];
+            a.out_probes = io.probes;
+        } else {
+            uint64_t span = nq * (uint64_t)a.m_fixed, maxlen = a.m_fixed;
+            if (ragged) {
+                span = maxlen = 0;
+                for (uint64_t k = 0; k < nq; k++) {
+                    uint64_t e = qoff[k] + qlen[k];
+                    if (e > span) span = e;
+                    if (qlen[k] > maxlen) maxlen = qlen[k];
+                }
+            }
+            qw = qw_for(maxlen);
+            a.m_max = maxlen ? (uint32_t)maxlen : 1;
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMalloc(&bqb.p, span + 64));
+            if (span) HIP_TRY(hipMemcpy(bqb.p, qbytes, span, hipMemcpyHostToDevice));
+            a.qbytes = static_cast<const uint8_t*>(bqb.p);
+            if (ragged) {
+                HIP_TRY(hipMalloc(&bqoff.p, nq * 8));
+                HIP_TRY(hipMalloc(&bqlen.p, nq * 4));
+                HIP_TRY(hipMemcpy(bqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(bqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
+                a.qoff = static_cast<const uint64_t*>(bqoff.p);
+                a.qlen = static_cast<const uint32_t*>(bqlen.p);
+            }
+            for (int i = 0; i < io.nout; i++) {
+                HIP_TRY(hipMalloc(&bout[i].p, nq * 8));
+                dev_out[i] = static_cast<uint64_t*>(bout[i].p);
+            }
+            if (io.probes) {
+                HIP_TRY(hipMalloc(&bprobes.p, nq * 4));
+                a.out_probes = static_cast<uint32_t*>(bprobes.p);
+            }
+        }
+        a.out_pos = dev_out[0];
+        if (check_bad) launch_validate(st, a, nq);  // every query byte, not only those a kernel packs
+        return 0;
+    }
+
+    int end(hipStream_t st, const SearchArgs& a, const char* what) {
+        if (!check_bad && dev) return 0;
+        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t hbad = 0;
+        if (check_bad) HIP_TRY(hipMemcpy(&hbad, a.bad, 4, hipMemcpyDeviceToHost));
+        if (!dev) {
+            for (int i = 0; i < io.nout; i++)
+                HIP_TRY(hipMemcpy(io.out[i], dev_out[i], a.nq * 8, hipMemcpyDeviceToHost));
+            if (io.probes) HIP_TRY(hipMemcpy(io.probes, a.out_probes, a.nq * 4, hipMemcpyDeviceToHost));
+        }
+        if (hbad) SAS_FAIL(EINVAL, std::string(what) + ": query bytes must be DNA codes 0..3");
+        return 0;
+    }
+};
+
 // queries t[qoff[k] .. qoff[k] + qlen[k]) of the indexed text (SAS_QUERIES_ARE_SLICES)
 __global__ void k_validate_slices(const uint64_t* __restrict__ qoff, const uint32_t* __restrict__ qlen, uint64_t nq,
                                   uint64_t n, uint32_t* __restrict__ bad) {
@@ -3581,23 +3751,17 @@ static int slices_impl(const sas_index* x, const uint64_t* qoff, const uint32_t*
     if (!qoff || !qlen) SAS_FAIL(EINVAL, "SAS_QUERIES_ARE_SLICES: null qoff/qlen");
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
+    SearchArgs a = fill_args(x, nq, 0);
     a.qoff = qoff;
     a.qlen = qlen;
     a.out_pos = out_pos;
     a.out_probes = out_probes;
-    a.bad = x->scratch;
     // every slice inside the text: checked first, always (an out-of-range slice would read
     // past the packed text); the call synchronises to read the flag back
     DeviceBuf bflag;
     HIP_TRY(hipMalloc(&bflag.p, 4));
     HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    uint64_t vb = (nq + 255) / 256;
-    if (vb > 65536) vb = 65536;
-    hipLaunchKernelGGL(k_validate_slices, dim3((unsigned)vb), dim3(256), 0, st, qoff, qlen, nq, x->n,
-                       static_cast<uint32_t*>(bflag.p));
+    launch(launch_ctx(nq, 256, 65536, st), k_validate_slices, qoff, qlen, nq, x->n, static_cast<uint32_t*>(bflag.p));
     uint32_t hbad = 0;
     HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3620,99 +3784,17 @@ static int search_impl(const sas_index* x, const uint8_t* qbytes, const uint64_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     bool dev = flags & SAS_DEVICE_PTRS;
 
-    if (!dev) {
-        // host arrays: the pinned, chunked pipeline (host_pipeline) unless one query alone
-        // exceeds a staging chunk
-        uint64_t maxlen = m_fixed;
-        if (ragged)
-            for (uint64_t k = 0; k < nq; k++) maxlen = qlen[k] > maxlen ? qlen[k] : maxlen;
-        if (maxlen <= SAS_STAGE_BYTES) {
-            const bool pack = !ragged && algo == SAS_ALGO_PREFIX && m_fixed > 0 && m_fixed <= 32 &&
-                              !(flags & SAS_PREFIX_RANGE);
-            return host_pipeline(x, ragged ? HM_RAGGED : (pack ? HM_PACK : HM_FIXED), qbytes, qoff, qlen, nullptr,
-                                 m_fixed, nq, algo, out_pos, out_probes, st, flags);
-        }
+    if (!dev && fits_stage(m_fixed, ragged ? qlen : nullptr, nq)) {
+        const bool pack = !ragged && algo == SAS_ALGO_PREFIX && m_fixed > 0 && m_fixed <= 32 &&
+                          !(flags & SAS_PREFIX_RANGE);
+        return host_pipeline(x, ragged ? HM_RAGGED : (pack ? HM_PACK : HM_FIXED), qbytes, qoff, qlen, nullptr,
+                             m_fixed, nq, algo, out_pos, out_probes, st, flags);
     }
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
-    a.m_fixed = m_fixed;
-    // invalid-code flag: a per-call word when it is read back, so that concurrent calls
-    // on other streams (allowed: the index is immutable) never see each other's flags;
-    // otherwise the index's write-only sink
-    a.bad = x->scratch;
-    bool check_bad = !dev || (flags & SAS_VALIDATE);
-    DeviceBuf bflag;
-    if (check_bad) {
-        HIP_TRY(hipMalloc(&bflag.p, 4));
-        HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-        a.bad = static_cast<uint32_t*>(bflag.p);
-    }
-
-    int qw = 4;
-    DeviceBuf bqb, bqoff, bqlen, bout, bprobes;
-    if (dev) {
-        a.qbytes = qbytes;
-        a.qoff = qoff;
-        a.qlen = qlen;
-        a.out_pos = out_pos;
-        a.out_probes = out_probes;
-        if (!ragged) qw = qw_for(m_fixed);
-        a.m_max = ragged ? 0 : m_fixed;
-    } else {
-        uint64_t span;
-        uint64_t maxlen = m_fixed;
-        if (ragged) {
-            span = 0;
-            maxlen = 0;
-            for (uint64_t k = 0; k < nq; k++) {
-                uint64_t e = qoff[k] + qlen[k];
-                if (e > span) span = e;
-                if (qlen[k] > maxlen) maxlen = qlen[k];
-            }
-        } else {
-            span = nq * (uint64_t)m_fixed;
-        }
-        qw = qw_for(maxlen);
-        a.m_max = maxlen ? (uint32_t)maxlen : 1;
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&bqb.p, span + 64));
-        if (span) HIP_TRY(hipMemcpy(bqb.p, qbytes, span, hipMemcpyHostToDevice));
-        a.qbytes = static_cast<const uint8_t*>(bqb.p);
-        if (ragged) {
-            HIP_TRY(hipMalloc(&bqoff.p, nq * 8));
-            HIP_TRY(hipMalloc(&bqlen.p, nq * 4));
-            HIP_TRY(hipMemcpy(bqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(bqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-            a.qoff = static_cast<const uint64_t*>(bqoff.p);
-            a.qlen = static_cast<const uint32_t*>(bqlen.p);
-        }
-        HIP_TRY(hipMalloc(&bout.p, nq * 8));
-        a.out_pos = static_cast<uint64_t*>(bout.p);
-        if (out_probes) {
-            HIP_TRY(hipMalloc(&bprobes.p, nq * 4));
-            a.out_probes = static_cast<uint32_t*>(bprobes.p);
-        }
-    }
-    if (check_bad) {  // every query byte, not only those the search kernel packs
-        uint64_t vb = (nq + 255) / 256;
-        if (vb > 65536) vb = 65536;
-        hipLaunchKernelGGL(k_validate_queries, dim3((unsigned)vb), dim3(256), 0, st, a.qbytes, a.qoff, a.qlen,
-                           a.m_fixed, nq, a.bad);
-    }
-    int rc = launch_search(x, a, algo, qw, flags, st);
-    if (rc) return rc;
-    if (check_bad || !dev) {
-        HIP_TRY(hipStreamSynchronize(st));
-        uint32_t hbad = 0;
-        if (check_bad) HIP_TRY(hipMemcpy(&hbad, a.bad, 4, hipMemcpyDeviceToHost));
-        if (!dev) {
-            HIP_TRY(hipMemcpy(out_pos, a.out_pos, nq * 8, hipMemcpyDeviceToHost));
-            if (out_probes) HIP_TRY(hipMemcpy(out_probes, a.out_probes, nq * 4, hipMemcpyDeviceToHost));
-        }
-        if (hbad) SAS_FAIL(EINVAL, "search: query bytes must be DNA codes 0..3");
-    }
-    return 0;
+    SearchArgs a = fill_args(x, nq, m_fixed);
+    DirectCall call;
+    TRY_RC(call.begin(x, st, flags, a, {qbytes, qoff, qlen, 1, {out_pos, nullptr}, out_probes}));
+    TRY_RC(launch_search(x, a, algo, call.qw, flags, st));
+    return call.end(st, a, "search");
 }
 
 extern "C" int sas_search_batch(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff,
@@ -3754,10 +3836,7 @@ extern "C" int sas_pack_queries(const uint8_t* qbytes, uint32_t m, uint64_t nq, 
     DeviceBuf bflag;
     HIP_TRY(hipMalloc(&bflag.p, 4));
     HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    uint64_t blocks = (nq + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_pack_queries, dim3((unsigned)blocks), dim3(256), 0, st, qbytes, m, nq, out_words,
-                       static_cast<uint32_t*>(bflag.p));
+    launch(launch_ctx(nq, 256, 65536, st), k_pack_queries, qbytes, m, nq, out_words, static_cast<uint32_t*>(bflag.p));
     HIP_TRY(hipGetLastError());
     uint32_t hbad = 0;
     HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
@@ -3779,11 +3858,7 @@ extern "C" int sas_search_packed(const sas_index* x, const uint64_t* qwords, uin
     if (!(flags & SAS_DEVICE_PTRS))  // host words: the pinned staging pipeline
         return host_pipeline(x, HM_WORDS, nullptr, nullptr, nullptr, qwords, m, nq, algo, out_pos, out_probes, st,
                              flags);
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
-    a.m_fixed = m;
-    a.bad = x->scratch;  // packed words hold no invalid codes
+    SearchArgs a = fill_args(x, nq, m);  // packed words hold no invalid codes: no flag of its own
     a.qwords = qwords;
     a.out_pos = out_pos;
     a.out_probes = out_probes;
@@ -3809,12 +3884,9 @@ extern "C" int sas_search_buckets(const sas_index* x, const void* queries, uint3
     if (cap >= (1ull << 32) || nq >= (1ull << 32)) SAS_FAIL(EINVAL, "sas_search_buckets: buckets x cap >= 2^32");
     if (!queries || !counts || !out_pos) SAS_FAIL(EINVAL, "sas_search_buckets: null argument");
     HIP_TRY(hipSetDevice(x->device));
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
-    a.m_fixed = m;
+    // device pointers: codes unchecked, as sas_search_fixed without SAS_VALIDATE
+    SearchArgs a = fill_args(x, nq, m);
     a.m_max = m;
-    a.bad = x->scratch;  // device pointers: codes unchecked, as sas_search_fixed without SAS_VALIDATE
     if (packed) a.qwords = static_cast<const uint64_t*>(queries);
     else a.qbytes = static_cast<const uint8_t*>(queries);
     a.out_pos = out_pos;
@@ -3830,14 +3902,10 @@ extern "C" int sas_time_fixed(const sas_index* x, const uint8_t* d_qbytes, uint3
     TRY_RC(check_algo(x, algo, flags, "sas_time_fixed"));
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
-    a.m_fixed = m;
+    SearchArgs a = fill_args(x, nq, m);
     a.m_max = m;
     a.qbytes = d_qbytes;
     a.out_pos = d_out_pos;
-    a.bad = x->scratch;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
@@ -4307,67 +4375,6 @@ extern "C" int sas_shard_gather(const sas_index* x, const uint64_t* back, const 
     return 0;
 }
 
-// ------------------------------------------------------------------ occurrence ranges
-template <bool KO, int W>
-static void launch_quad_range(int qw, dim3 grid, dim3 block, hipStream_t st, const SearchArgs& a, uint64_t* dhi) {
-    switch (qw) {
-        case 1: hipLaunchKernelGGL((k_sa_quad_range<1, KO, W>), grid, block, 0, st, a, dhi); break;
-        case 2: hipLaunchKernelGGL((k_sa_quad_range<2, KO, W>), grid, block, 0, st, a, dhi); break;
-        case 4: hipLaunchKernelGGL((k_sa_quad_range<4, KO, W>), grid, block, 0, st, a, dhi); break;
-        default: hipLaunchKernelGGL((k_sa_quad_range<8, KO, W>), grid, block, 0, st, a, dhi); break;
-    }
-}
-
-// Occurrence-range kernel for the index's structures (a.nq queries; lo to a.out_pos, hi to dhi)
-static void launch_range(const sas_index* x, const SearchArgs& a, int qw, uint32_t flags, hipStream_t st,
-                         uint64_t* dhi) {
-    const bool quad = x->quad_leaves != nullptr;
-    // the prefix table, when built, replaces the two tree descents (one lane per query;
-    // G lanes per query on a G-slot inline table)
-    const bool ptab = quad && x->prefix && !(flags & SAS_NO_PREFIX_TABLE);
-    const bool pair = ptab && !x->quad_compact && (x->prefix_w == 32 || x->prefix_w == 64) &&
-                      !(flags & SAS_RANGE_NO_INLINE);
-    const uint64_t per = (quad && !ptab) ? QUAD_G : (pair ? x->prefix_w / 16 : 1);
-    uint64_t blocks = (a.nq * per + SEARCH_BLOCK - 1) / SEARCH_BLOCK;
-    uint64_t cap = (uint64_t)x->num_cus * BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    dim3 grid((unsigned)blocks), block(SEARCH_BLOCK);
-    if (x->tag_lines) {
-        switch (qw) {
-            case 1: hipLaunchKernelGGL(k_sa_tagged_lines_range<1>, grid, block, 0, st, a, dhi); break;
-            case 2: hipLaunchKernelGGL(k_sa_tagged_lines_range<2>, grid, block, 0, st, a, dhi); break;
-            case 4: hipLaunchKernelGGL(k_sa_tagged_lines_range<4>, grid, block, 0, st, a, dhi); break;
-            default: hipLaunchKernelGGL(k_sa_tagged_lines_range<8>, grid, block, 0, st, a, dhi); break;
-        }
-    } else if (x->tag_table) {
-        switch (qw) {
-            case 1: hipLaunchKernelGGL(k_sa_tagged_range<1>, grid, block, 0, st, a, dhi); break;
-            case 2: hipLaunchKernelGGL(k_sa_tagged_range<2>, grid, block, 0, st, a, dhi); break;
-            case 4: hipLaunchKernelGGL(k_sa_tagged_range<4>, grid, block, 0, st, a, dhi); break;
-            default: hipLaunchKernelGGL(k_sa_tagged_range<8>, grid, block, 0, st, a, dhi); break;
-        }
-    } else if (pair) {
-        if (x->prefix_w == 32) launch_prefix2_range<2>(qw, grid, block, st, a, dhi);
-        else launch_prefix2_range<4>(qw, grid, block, st, a, dhi);
-    } else if (ptab) {
-        if (!x->quad_compact) launch_prefix_range<false, 4>(qw, grid, block, st, a, dhi);
-        else if (x->sa_w == 5) launch_prefix_range<true, 5>(qw, grid, block, st, a, dhi);
-        else launch_prefix_range<true, 4>(qw, grid, block, st, a, dhi);
-    } else if (quad && !x->quad_compact) {
-        launch_quad_range<false, 4>(qw, grid, block, st, a, dhi);
-    } else if (quad) {
-        if (x->sa_w == 5) launch_quad_range<true, 5>(qw, grid, block, st, a, dhi);
-        else launch_quad_range<true, 4>(qw, grid, block, st, a, dhi);
-    } else {
-        switch (qw) {
-            case 1: hipLaunchKernelGGL(k_sa_sector_range<1>, grid, block, 0, st, a, dhi); break;
-            case 2: hipLaunchKernelGGL(k_sa_sector_range<2>, grid, block, 0, st, a, dhi); break;
-            case 4: hipLaunchKernelGGL(k_sa_sector_range<4>, grid, block, 0, st, a, dhi); break;
-            default: hipLaunchKernelGGL(k_sa_sector_range<8>, grid, block, 0, st, a, dhi); break;
-        }
-    }
-}
-
 // ragged (qoff, qlen) or fixed-length (qoff == nullptr: m_fixed chars per query)
 static int range_impl(const sas_index* x, const uint8_t* qbytes, uint32_t m_fixed, const uint64_t* qoff,
                       const uint32_t* qlen, uint64_t nq, uint64_t* out_lo, uint64_t* out_hi, void* stream,
@@ -4382,83 +4389,15 @@ static int range_impl(const sas_index* x, const uint8_t* qbytes, uint32_t m_fixe
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     bool dev = flags & SAS_DEVICE_PTRS;
-    if (!dev) {
-        // host arrays: the pinned, chunked pipeline unless one query alone exceeds a chunk
-        uint64_t maxlen = m_fixed;
-        if (ragged)
-            for (uint64_t k = 0; k < nq; k++) maxlen = qlen[k] > maxlen ? qlen[k] : maxlen;
-        if (maxlen <= SAS_STAGE_BYTES)
-            return host_pipeline(x, ragged ? HM_RAGGED : HM_FIXED, qbytes, qoff, qlen, nullptr, m_fixed, nq, -1,
-                                 out_lo, nullptr, st, flags, out_hi);
-    }
-    SearchArgs a{};
-    fill_args(x, a);
-    a.nq = nq;
-    a.m_fixed = ragged ? 0 : m_fixed;
-    a.bad = x->scratch;  // per-call flag when read back (see search_impl)
-    bool check_bad = !dev || (flags & SAS_VALIDATE);
-    DeviceBuf bflag;
-    if (check_bad) {
-        HIP_TRY(hipMalloc(&bflag.p, 4));
-        HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-        a.bad = static_cast<uint32_t*>(bflag.p);
-    }
-    DeviceBuf bqb, bqoff, bqlen, blo, bhi;
-    uint64_t* dhi = out_hi;
-    int qw = ragged ? 4 : qw_for(m_fixed);
-    if (dev) {
-        a.qbytes = qbytes;
-        a.qoff = qoff;
-        a.qlen = qlen;
-        a.out_pos = out_lo;
-    } else {
-        uint64_t span = nq * (uint64_t)m_fixed, maxlen = m_fixed;
-        if (ragged) {
-            span = maxlen = 0;
-            for (uint64_t k = 0; k < nq; k++) {
-                uint64_t e = qoff[k] + qlen[k];
-                if (e > span) span = e;
-                if (qlen[k] > maxlen) maxlen = qlen[k];
-            }
-        }
-        qw = qw_for(maxlen);
-        a.m_max = maxlen ? (uint32_t)maxlen : 1;
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&bqb.p, span + 64));
-        if (span) HIP_TRY(hipMemcpy(bqb.p, qbytes, span, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&blo.p, nq * 8));
-        HIP_TRY(hipMalloc(&bhi.p, nq * 8));
-        a.qbytes = static_cast<const uint8_t*>(bqb.p);
-        if (ragged) {
-            HIP_TRY(hipMalloc(&bqoff.p, nq * 8));
-            HIP_TRY(hipMalloc(&bqlen.p, nq * 4));
-            HIP_TRY(hipMemcpy(bqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(bqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-            a.qoff = static_cast<const uint64_t*>(bqoff.p);
-            a.qlen = static_cast<const uint32_t*>(bqlen.p);
-        }
-        a.out_pos = static_cast<uint64_t*>(blo.p);
-        dhi = static_cast<uint64_t*>(bhi.p);
-    }
-    if (check_bad) {
-        uint64_t vb = (nq + 255) / 256;
-        if (vb > 65536) vb = 65536;
-        hipLaunchKernelGGL(k_validate_queries, dim3((unsigned)vb), dim3(256), 0, st, a.qbytes, a.qoff, a.qlen,
-                           a.m_fixed, nq, a.bad);
-    }
-    launch_range(x, a, qw, flags, st, dhi);
+    if (!dev && fits_stage(m_fixed, ragged ? qlen : nullptr, nq))
+        return host_pipeline(x, ragged ? HM_RAGGED : HM_FIXED, qbytes, qoff, qlen, nullptr, m_fixed, nq, -1, out_lo,
+                             nullptr, st, flags, out_hi);
+    SearchArgs a = fill_args(x, nq, ragged ? 0 : m_fixed);
+    DirectCall call;
+    TRY_RC(call.begin(x, st, flags, a, {qbytes, ragged ? qoff : nullptr, qlen, 2, {out_lo, out_hi}, nullptr}));
+    launch_range(x, a, call.qw, flags, st, call.dev_out[1]);
     HIP_TRY(hipGetLastError());
-    if (check_bad || !dev) {
-        HIP_TRY(hipStreamSynchronize(st));
-        uint32_t hbad = 0;
-        if (check_bad) HIP_TRY(hipMemcpy(&hbad, a.bad, 4, hipMemcpyDeviceToHost));
-        if (!dev) {
-            HIP_TRY(hipMemcpy(out_lo, a.out_pos, nq * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(out_hi, dhi, nq * 8, hipMemcpyDeviceToHost));
-        }
-        if (hbad) SAS_FAIL(EINVAL, "sas_search_range: query bytes must be DNA codes 0..3");
-    }
-    return 0;
+    return call.end(st, a, "sas_search_range");
 }
 
 extern "C" int sas_search_range(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,

@@ -1403,3 +1403,58 @@ def test_llcp_tails_short_suffixes_and_probes(sas):
         assert (pr >= layers).all(), (algo, int(pr.min()))
         assert (pr <= 2 * layers + 4 + lvl + 2).all(), (algo, int(pr.max()))
     idx.free()
+
+
+def test_dispatch_matrix(sas):
+    """The host dispatch, pinned: which kernel instance a call launches depends on the query
+    words qw_for gives its longest query (1, 2, 4, 8: lengths each side of 32, 64 and 128, and
+    one past the 256 chars the registers hold), on whether the batch's longest query is known
+    (fixed-length device calls: the register-resident variants; ragged device calls: unknown,
+    the repacking ones; host calls: known from the scan) and on the index's SA width and leaf
+    format.  Every algorithm and the occurrence ranges, called those three ways on a u32, a
+    40-bit, a compact-leaf and a tagged index (entries and bucket lines) over a random and a
+    7-periodic text, equal the oracle's binary_search / prefix range on the oracle-built SA."""
+    import torch
+    rng = np.random.default_rng(2024)
+    n = 1 << 14
+    per = rng.integers(0, 4, 7, dtype=np.uint8)
+    per[1] = (per[0] + 1) % 4  # never a run of one char
+    compact = dict(lcp=False, stree=False, sector=False, quad="compact")
+    plan = (  # index, build arguments, algorithms
+        ("u32", {}, ALGOS), ("sa40", dict(sa40=True), ALGOS),
+        ("compact", compact, ("plain", "lcp", "quad", "inline", "prefix", "interp")),
+        ("compact40", dict(sa40=True, **compact), ("plain", "lcp", "quad", "inline", "prefix", "interp")),
+        ("tagged", dict(tagged=True, lcp=False), ("tagged", "plain", "lcp", "interp")),
+        ("tag_lines", dict(tagged=True, lcp=False, tag_lines=True), ("tagged",)))
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).cuda()
+    host = lambda x: x.cpu().numpy().astype(np.uint64)
+    for name, t in (("random", O.random_string(n, seed=31)), ("period_7", np.tile(per, n // 7 + 1)[:n])):
+        sa = O.build_sa(t)
+        tp = O.padded(t)
+        idxs = [(kind, sas.SaNaive.build(t, **kw), algos) for kind, kw, algos in plan]
+        for m in (1, 32, 33, 64, 65, 128, 129, 256, 300):
+            qs = [t[o:o + m] for o in rng.integers(0, n - m, 127)] + [t[n - m:]]
+            for j, q in enumerate(qs[:96]):  # one char changed: the first, the last, or any
+                mq = q.copy()
+                mq[(0, m - 1, int(rng.integers(0, m)))[j % 3]] ^= int(rng.integers(1, 4))
+                qs.append(mq)
+            for k in rng.integers(1, m + 1, 32):  # a text-end suffix, and what follows it in a longer query
+                qs.append(np.concatenate([t[n - k:], rng.integers(0, 4, m - k, dtype=np.uint8)]))
+            assert len(qs) == 256 and all(len(q) == m for q in qs)
+            buf, off, lens = pack(qs)
+            epos = oracle_positions(t, sa, buf[:-64], off, lens)
+            erange = np.array([O.prefix_range(tp, n, sa, q) for q in qs], np.uint64)
+            dbuf, doff, dlen = dev(buf[:-64], np.uint8), dev(off, np.int64), dev(lens, np.int32)
+            for kind, idx, algos in idxs:
+                for algo in algos:
+                    where = (name, m, kind, algo)
+                    assert np.array_equal(host(idx.search_fixed(dbuf, m, algo=algo)), epos), where + ("fixed",)
+                    assert np.array_equal(host(idx.search_batch(dbuf, doff, dlen, algo=algo)), epos), where + ("ragged",)
+                    assert np.array_equal(idx.search_batch(buf, off, lens, algo=algo), epos), where + ("host",)
+                for way, (lo, hi) in (("fixed", idx.search_range_fixed(dbuf, m)),
+                                      ("ragged", idx.search_range(dbuf, doff, dlen)),
+                                      ("host", idx.search_range(buf, off, lens))):
+                    got = np.stack([lo if way == "host" else host(lo), hi if way == "host" else host(hi)], 1)
+                    assert np.array_equal(got, erange), (name, m, kind, way)
+        for _, idx, _ in idxs:
+            idx.free()
