@@ -477,6 +477,39 @@ int sas_locate_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, 
                      uint64_t max_per_query, uint64_t* out_off, void* out_pos, uint64_t capacity,
                      uint64_t* out_total, void* stream, uint32_t flags);
 
+/* Longest-prefix match: how much of each query occurs in the text, and where.  With lb = the
+ * number of suffixes < q (the rank the searches use), a = lcp(q, t[SA[lb-1]..]) (0 if
+ * lb == 0) and b = lcp(q, t[SA[lb]..]) (0 if lb == n), lcps capped by both lengths:
+ *   out_len[k] = max(a, b), the length of the longest prefix of query k that occurs anywhere
+ *                in the text (it is always an lcp with one of those two neighbours);
+ *   out_pos[k] = a text position where that prefix occurs: SA[lb] if lb < n and b == len, else
+ *                SA[lb-1]; n when len == 0;
+ *   [out_lo[k], out_hi[k]) = the SA ranks of every suffix that starts with q[0 .. len), what
+ *                sas_search_range returns for that prefix ([0, n) when len == 0).
+ * out_pos, out_lo and out_hi may each be NULL.  One lower-bound search per query that keeps
+ * the exact lcps of its bounds, started from the prefix table's range when the index has one
+ * and the query has at least p chars (SAS_NO_PREFIX_TABLE: always from [0, n), an A/B and
+ * test hook); the ranges are one sas_search_range over the same bytes with out_len as the
+ * lengths.  Needs a whole index (no shard, no part) with a u32 or packed 40-bit SA array;
+ * SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES indexes return ENOTSUP.  out_lo / out_hi also need
+ * what sas_search_range needs (its error is returned otherwise).  With SAS_DEVICE_PTRS:
+ * asynchronous on `stream`, scratch from the index's stream-ordered pool; SAS_VALIDATE
+ * rejects query bytes > 3 (synchronises).  With host pointers: synchronous, bytes always
+ * validated.  Ragged queries may overlap in qbytes.
+ *
+ * sas_match_stats, the matching statistics of a pattern: query i = pattern[i .. min(i +
+ * max_len, plen)) for every i in [0, plen); the outputs have plen entries. */
+int sas_match(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+              uint64_t nq, uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi,
+              void* stream, uint32_t flags);
+/* sas_match for fixed-length queries qbytes[k*m .. (k+1)*m). */
+int sas_match_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq,
+                    uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi,
+                    void* stream, uint32_t flags);
+int sas_match_stats(const sas_index* index, const uint8_t* pattern, uint64_t plen, uint32_t max_len,
+                    uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi,
+                    void* stream, uint32_t flags);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

@@ -9,6 +9,7 @@
  *   sas::bench / sas::bench_batch         bench / bench_batch         sas/sa_search.rs:423-451
  *   SaNaive::search / search_prefix       Search::search/_prefix      sas/util.rs:29-47
  *   SaNaive::locate / search_between      search_prefix for a whole batch (CSR) / Search::search_range(Range)
+ *   SaNaive::match                        longest-prefix match of a whole batch (sas_match; no counterpart)
  *   sas::random_string / random_queries   util.rs:9-26 (ChaCha8Rng::seed_from_u64(31415), main.rs:38)
  *   sas::read_fasta_file                  util.rs:144-169
  *   sst::SortedVec / Eytzinger / STree16 / STree15 / PartitionedSTree16M / DirectMap /
@@ -226,6 +227,39 @@ class SaNaive {
         if (total)
             check(sas_locate(h_, bytes.data(), qoff.data(), len.data(), qs.size(), max_per_query, r.off.data(),
                              r.pos.data(), total, &total, nullptr, 0));
+        return r;
+    }
+
+    /* longest-prefix match of query k: q[0 .. len) is the longest prefix that occurs in the text,
+     * pos one position where it does (n when len == 0), [lo, hi) the SA ranks of every suffix
+     * that starts with it */
+    struct Matched {
+        std::vector<uint32_t> len;
+        std::vector<uint64_t> pos, lo, hi;
+    };
+
+    /* how much of each query occurs, and where, in one call (sas_match); ranges = false leaves
+     * lo / hi empty (no tree needed) */
+    Matched match(const std::vector<Seq>& qs, bool ranges = true, uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Matched r;
+        r.len.assign(qs.size(), 0);
+        r.pos.assign(qs.size(), 0);
+        if (ranges) {
+            r.lo.assign(qs.size(), 0);
+            r.hi.assign(qs.size(), 0);
+        }
+        if (!qs.empty())
+            check(sas_match(h_, bytes.data(), qoff.data(), len.data(), qs.size(), r.len.data(), r.pos.data(),
+                            ranges ? r.lo.data() : nullptr, ranges ? r.hi.data() : nullptr, nullptr, flags));
         return r;
     }
 

@@ -307,6 +307,60 @@ __device__ __forceinline__ void sa_put(uint8_t* p, uint64_t i, uint64_t v) {
     for (int k = 0; k < 5; k++) b[k] = (uint8_t)(v >> (8 * k));
 }
 
+// ---------------------------------------------------------------- prefix table lookups
+// The SAS_BUILD_PREFIX table as a lookup reads it (the kernels' argument structs fill one):
+// entry j = the first rank whose p-char key (zero padded past a suffix's end, so key order is
+// SA order) is >= base + j, in any of the entry formats of build_prefix (sas_build.hip)
+struct PrefixView {
+    const uint8_t* prefix;   // u32 or packed 40-bit entries, or 16 G-byte inline ones
+    uint32_t prefix_chars;
+    uint32_t prefix_w;       // bytes per table entry (4, 5, or 16 G)
+    uint32_t prefix_hi40;    // inline slots: SA bits 32..39 in slot 1's rank word
+    uint64_t pt_base;        // the table's first key (0, or a part's first suffix's key)
+    uint64_t pt_jmax;        // its last entry a lookup may start at (entries - 2)
+};
+// The table entry of p-char key K: K - pt_base, clamped to the table.  A whole index's table
+// holds every key (pt_base 0, pt_jmax 4^p - 1: the identity).  A part's holds its first
+// suffix's key .. its last one's and two entries of rank sa_n: a key below the interval
+// clamps to entry 0, whose suffixes (like every suffix of the part) are > q, so the lower
+// bound is rank 0 from either; a key above it to entry jmax, the empty range at sa_n
+__device__ __forceinline__ uint64_t pt_slot(const PrefixView& a, uint64_t K) {
+    K = K > a.pt_base ? K - a.pt_base : 0;
+    return K < a.pt_jmax ? K : a.pt_jmax;
+}
+// Rank of inline entry j (16 G bytes): slot 0's rank word, and for two slots beside a text of
+// >= 2^32 chars bits 32..39 from slot 1's (a part of >= 2^32 suffixes)
+template <int G, bool HI40>
+__device__ __forceinline__ uint64_t pt_rank(const uint4* t, uint64_t j) {
+    const uint64_t r = t[G * j].z;
+    if (!(HI40 && G == 2)) return r;
+    return r | ((uint64_t)((t[G * j + 1].z >> 16) & 0xFFu) << 32);
+}
+// prefix_range (sas/sa_search.rs:86-95): the SA ranks [lo, hi) whose p-char key is K,
+// from the prefix table in any of its entry formats
+__device__ __forceinline__ void prefix_range(const PrefixView& a, uint64_t K, uint64_t* lo, uint64_t* hi) {
+    K = pt_slot(a, K);
+    if (a.prefix_w >= 16) {  // inline entries: rank in the first slot's .z
+        const uint4* t = reinterpret_cast<const uint4*>(a.prefix);
+        if (a.prefix_w == 32 && a.prefix_hi40) {
+            *lo = pt_rank<2, true>(t, K);
+            *hi = pt_rank<2, true>(t, K + 1);
+        } else {
+            const uint64_t st = a.prefix_w / 16;
+            *lo = t[st * K].z;
+            *hi = t[st * (K + 1)].z;
+        }
+    } else if (a.prefix_w == 5) {
+        const SaView<5> v{a.prefix};
+        *lo = v[K];
+        *hi = v[K + 1];
+    } else {
+        const uint32_t* t = reinterpret_cast<const uint32_t*>(a.prefix);
+        *lo = t[K];
+        *hi = t[K + 1];
+    }
+}
+
 // ---------------------------------------------------------------- 4-lane (quad) groups
 #define QUAD_G 4
 

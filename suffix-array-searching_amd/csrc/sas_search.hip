@@ -120,6 +120,10 @@ struct SearchArgs {
     uint32_t* bad;
     const uint64_t* bcounts; // sas_search_buckets: queries per bucket (null: every slot is a query)
     uint32_t bcap;           // slots per bucket
+    // the prefix table as common.hpp's lookups read it
+    __host__ __device__ __forceinline__ PrefixView pt() const {
+        return PrefixView{prefix, prefix_chars, prefix_w, prefix_hi40, pt_base, pt_jmax};
+    }
 };
 
 // sas_search_buckets (the sharded step's received slots): slot i is place i % bcap of
@@ -167,46 +171,11 @@ __device__ __forceinline__ bool llcp_tie_less(const uint64_t* __restrict__ tw, u
     return lenS < (uint64_t)q.m;
 }
 
-// The table entry of p-char key K: K - pt_base, clamped to the table.  A whole index's table
-// holds every key (pt_base 0, pt_jmax 4^p - 1: the identity).  A part's holds its first
-// suffix's key .. its last one's and two entries of rank sa_n: a key below the interval
-// clamps to entry 0, whose suffixes (like every suffix of the part) are > q, so the lower
-// bound is rank 0 from either; a key above it to entry jmax, the empty range at sa_n
-__device__ __forceinline__ uint64_t pt_slot(const SearchArgs& a, uint64_t K) {
-    K = K > a.pt_base ? K - a.pt_base : 0;
-    return K < a.pt_jmax ? K : a.pt_jmax;
-}
-// Rank of inline entry j (16 G bytes): slot 0's rank word, and for two slots beside a text of
-// >= 2^32 chars bits 32..39 from slot 1's (a part of >= 2^32 suffixes)
-template <int G, bool HI40>
-__device__ __forceinline__ uint64_t pt_rank(const uint4* t, uint64_t j) {
-    const uint64_t r = t[G * j].z;
-    if (!(HI40 && G == 2)) return r;
-    return r | ((uint64_t)((t[G * j + 1].z >> 16) & 0xFFu) << 32);
-}
-// prefix_range (sas/sa_search.rs:86-95): the SA ranks [lo, hi) whose p-char key is K,
-// from the prefix table in any of its entry formats
+// The prefix table lookups live in common.hpp (PrefixView: pt_slot, pt_rank, prefix_range);
+// the kernels here hand them the view of their SearchArgs
+__device__ __forceinline__ uint64_t pt_slot(const SearchArgs& a, uint64_t K) { return pt_slot(a.pt(), K); }
 __device__ __forceinline__ void prefix_range(const SearchArgs& a, uint64_t K, uint64_t* lo, uint64_t* hi) {
-    K = pt_slot(a, K);
-    if (a.prefix_w >= 16) {  // inline entries: rank in the first slot's .z
-        const uint4* t = reinterpret_cast<const uint4*>(a.prefix);
-        if (a.prefix_w == 32 && a.prefix_hi40) {
-            *lo = pt_rank<2, true>(t, K);
-            *hi = pt_rank<2, true>(t, K + 1);
-        } else {
-            const uint64_t st = a.prefix_w / 16;
-            *lo = t[st * K].z;
-            *hi = t[st * (K + 1)].z;
-        }
-    } else if (a.prefix_w == 5) {
-        const SaView<5> v{a.prefix};
-        *lo = v[K];
-        *hi = v[K + 1];
-    } else {
-        const uint32_t* t = reinterpret_cast<const uint32_t*>(a.prefix);
-        *lo = t[K];
-        *hi = t[K + 1];
-    }
+    prefix_range(a.pt(), K, lo, hi);
 }
 
 // MODE 0: PLAIN, 1: LCP (mlr), 2: LLCP (Manber-Myers with the Llcp/Rlcp entries)

@@ -166,6 +166,9 @@ def lib():
     L.sas_locate_fill.argtypes = [vp, vp, vp, u64, vp, u64, vp, u32]
     L.sas_locate.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, u32]
     L.sas_locate_fixed.argtypes = [vp, vp, u32, u64, u64, vp, vp, u64, vp, vp, u32]
+    L.sas_match.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u32]
+    L.sas_match_fixed.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, u32]
+    L.sas_match_stats.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, vp, u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

@@ -652,6 +652,63 @@ class SaNaive:
         _, pos = self.locate_ranges(dlo, dhi)
         return pos.cpu().numpy().astype(np.uint64)
 
+    # -- longest-prefix match and matching statistics (sas_match*)
+    def _match(self, kind, qbytes, qoff, qlen, m, nq, ranges, stream, flags):
+        dev = _is_cuda(qbytes)
+        if dev:
+            import torch
+            d = qbytes.device
+            ln = torch.empty(nq, dtype=torch.int32, device=d)
+            pos = torch.empty(nq, dtype=torch.int64, device=d)
+            lo = torch.empty(nq, dtype=torch.int64, device=d) if ranges else None
+            hi = torch.empty(nq, dtype=torch.int64, device=d) if ranges else None
+            st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+            flags |= _lib.SAS_DEVICE_PTRS
+        else:
+            qbytes = _as_u8(qbytes)
+            ln = np.zeros(max(nq, 1), np.uint32)
+            pos = np.zeros(max(nq, 1), np.uint64)
+            lo = np.zeros(max(nq, 1), np.uint64) if ranges else None
+            hi = np.zeros(max(nq, 1), np.uint64) if ranges else None
+            st = stream
+        outs = (_ptr(ln), _ptr(pos), _ptr(lo), _ptr(hi), st, flags)
+        if kind == "ragged":
+            rc = lib().sas_match(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *outs)
+        elif kind == "fixed":
+            rc = lib().sas_match_fixed(self._h, _ptr(qbytes), m, nq, *outs)
+        else:
+            rc = lib().sas_match_stats(self._h, _ptr(qbytes), nq, m, *outs)
+        check(rc)
+        res = (ln, pos, lo, hi) if ranges else (ln, pos)
+        return res if dev else tuple(r[:nq] for r in res)
+
+    def match(self, qbytes, qoff, qlen, ranges: bool = True, stream=None, flags: int = 0):
+        """Longest-prefix match of ragged queries qbytes[qoff[k] : qoff[k] + qlen[k]] (sas_match):
+        (len, pos) or with ranges (len, pos, lo, hi).  len[k] is the length of the longest prefix
+        of query k that occurs in the text, pos[k] a position where it occurs (n when len is 0),
+        [lo[k], hi[k]) the SA ranks of every suffix starting with that prefix.  numpy in -> numpy
+        out (uint32 len, uint64 others; synchronous); torch CUDA in (uint8 bytes, int64 qoff,
+        int32 qlen) -> CUDA out (int32 len, int64 others; async on `stream`)."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._match("ragged", qbytes, qoff, qlen, 0, nq, ranges, stream, flags)
+
+    def match_fixed(self, qbytes, m: int, ranges: bool = True, stream=None, flags: int = 0):
+        """match for fixed-length queries qbytes[k*m : (k+1)*m] (sas_match_fixed)."""
+        if m <= 0:
+            raise ValueError("use match for empty queries")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._match("fixed", qbytes, None, None, int(m), nq, ranges, stream, flags)
+
+    def match_stats(self, pattern, max_len: int, ranges: bool = True, stream=None, flags: int = 0):
+        """Matching statistics of `pattern` (sas_match_stats): match of the queries
+        pattern[i : min(i + max_len, len(pattern))] for every i, one entry per pattern char."""
+        plen = int(pattern.numel() if _is_cuda(pattern) else len(pattern))
+        return self._match("stats", pattern, None, None, int(max_len), plen, ranges, stream, flags)
+
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
         kn, cn = C.c_double(0), C.c_double(0)
