@@ -510,6 +510,56 @@ int sas_match_stats(const sas_index* index, const uint8_t* pattern, uint64_t ple
                     uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi,
                     void* stream, uint32_t flags);
 
+/* k-mismatch locate (Hamming distance): every alignment of every query with at most k
+ * substituted chars, by seed and verify.  An alignment of a query q of m chars is a text
+ * position s with s + m <= n; its distance is the number of j < m with q[j] != t[s + j] (an
+ * alignment never runs past the text end: the padding behind the text matches nothing).
+ * The query is cut into k + 1 pieces, piece j = chars [b_j, b_{j+1}) with b_j = floor(j m /
+ * (k + 1)); an alignment of distance <= k matches at least one piece exactly, so the
+ * occurrences of the pieces (one sas_search_range over all of them) are the candidates, and
+ * one kernel verifies them against the packed text, 32 chars per XOR and popcount.
+ *   - a piece that occurs more than max_seed_hits times in the text (its whole SA range;
+ *     max_seed_hits == 0: no limit) is skipped as a seed and its query flagged
+ *     SAS_MM_TRUNCATED;
+ *   - a query with m <= k (the empty query at every k) has no k + 1 non-empty pieces: it gets
+ *     no result and the flag SAS_MM_SHORT;
+ *   - the answer of a query is every alignment of distance <= k at which at least one
+ *     non-skipped piece matches exactly: for an unflagged query the complete k-mismatch
+ *     answer.  Each alignment is reported once, by the first non-skipped piece that matches
+ *     exactly there, and a query's results are ordered by (that piece, the SA rank of its
+ *     occurrence).  With k == 0 and max_seed_hits == 0 the positions of a non-empty query are
+ *     sas_locate's, in its order.
+ * Results in CSR form as sas_locate gives them: out_off[0..nq] (u64), out_pos (u64, or u32
+ * with SAS_LOCATE_U32), out_dist (one byte per position: its distance; may be NULL) and
+ * out_qflags (one byte per query: SAS_MM_*; may be NULL).  k is 0..15 (EINVAL above).  Flags:
+ * SAS_DEVICE_PTRS, SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE.  Needs what
+ * sas_search_range needs (its error is returned otherwise) on a whole index (no shard, no
+ * part) with a u32 or packed 40-bit SA array; SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES indexes
+ * return ENOTSUP.
+ * With host pointers: synchronous, bytes always validated; *out_total is always set, out_off
+ * and out_qflags always filled; if the total exceeds `capacity` nothing is copied to out_pos /
+ * out_dist and the call returns ENOSPC (out_pos == NULL, capacity == 0 is the sizing call).
+ * With SAS_DEVICE_PTRS: scratch from the index's stream-ordered pool; nothing at or past
+ * `capacity` is written; out_total (device, may be NULL) = out_off[nq], which the caller
+ * checks against `capacity` afterwards.  The call synchronises on `stream` ONCE, to read
+ * the number of candidates (the occurrences of all seeds) back to the host: it sizes the
+ * candidate scratch and the grids.  Nothing else synchronises unless SAS_VALIDATE is set. */
+#define SAS_MM_TRUNCATED 1u /* out_qflags: a seed was skipped (more than max_seed_hits hits) */
+#define SAS_MM_SHORT     2u /* out_qflags: m <= k, no result                                  */
+int sas_locate_mismatch(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                        uint64_t nq, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off, void* out_pos,
+                        uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
+                        void* stream, uint32_t flags);
+/* sas_locate_mismatch for fixed-length queries qbytes[k*m .. (k+1)*m). */
+int sas_locate_mismatch_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                              uint64_t max_seed_hits, uint64_t* out_off, void* out_pos, uint8_t* out_dist,
+                              uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
+                              uint32_t flags);
+/* Timing helper for benches: with SAS_MM_TIMING=1 in the environment every sas_locate_mismatch*
+ * call times its verify kernel with HIP events (and synchronises to do so); this returns the
+ * calling thread's last figure in ms (< 0: none) and the candidates it verified. */
+double sas_locate_mismatch_verify_ms(uint64_t* candidates);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

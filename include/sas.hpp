@@ -263,6 +263,45 @@ class SaNaive {
         return r;
     }
 
+    /* CSR result of locate_mismatch: query k's alignments are pos[off[k] .. off[k+1]) with their
+     * Hamming distances in dist, ordered by (reporting piece, SA rank); qflags[k] is a mask of
+     * SAS_MM_TRUNCATED and SAS_MM_SHORT */
+    struct Mismatched {
+        std::vector<uint64_t> off, pos;
+        std::vector<uint8_t> dist, qflags;
+    };
+
+    /* every alignment of every query with at most k substituted chars, in one call
+     * (sas_locate_mismatch: seed and verify on the GPU); a seed that occurs more than
+     * max_seed_hits times is skipped (0: no limit) */
+    Mismatched locate_mismatch(const std::vector<Seq>& qs, uint32_t k, uint64_t max_seed_hits = 0,
+                               uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Mismatched r;
+        r.off.assign(qs.size() + 1, 0);
+        r.qflags.assign(qs.size(), 0);
+        uint64_t total = 0;
+        /* the sizing call (ENOSPC unless nothing aligns), then the real one */
+        const int rc = sas_locate_mismatch(h_, bytes.data(), qoff.data(), len.data(), qs.size(), k, max_seed_hits,
+                                           r.off.data(), nullptr, nullptr, r.qflags.data(), 0, &total, nullptr, flags);
+        if (rc != ENOSPC) check(rc);
+        r.pos.resize(total);
+        r.dist.resize(total);
+        if (total)
+            check(sas_locate_mismatch(h_, bytes.data(), qoff.data(), len.data(), qs.size(), k, max_seed_hits,
+                                      r.off.data(), r.pos.data(), r.dist.data(), r.qflags.data(), total, &total,
+                                      nullptr, flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are

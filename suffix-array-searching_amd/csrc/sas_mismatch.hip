@@ -1,0 +1,562 @@
+// sas_mismatch.hip -- k-mismatch locate (Hamming distance) by seed and verify (sas.h:
+// sas_locate_mismatch, sas_locate_mismatch_fixed).
+//
+// A query of m chars with a budget of k substitutions is cut into k + 1 pieces, piece j =
+// chars [b_j, b_{j+1}) with b_j = floor(j m / (k + 1)).  An alignment with at most k mismatches
+// matches at least one piece exactly (pigeonhole), so the occurrences of the pieces are the
+// only candidates:
+//
+//   1. k_mm_pieces     offsets and lengths of the nq (k + 1) pieces (ragged queries that overlap
+//                      in the caller's bytes, which the range search takes);
+//   2. sas_search_range over all pieces: their SA rank ranges;
+//   3. k_mm_gate       empties the range of every piece that occurs more than max_seed_hits
+//                      times (a skipped seed) and of every piece of a query with m <= k; writes
+//                      the per-query flags and a per-query mask of skipped pieces;
+//   4. sas_locate_offsets on the gated ranges: the candidate offsets, one candidate per
+//                      occurrence of a piece; the host reads the candidate total C (the call's
+//                      one read-back: it sizes the candidate scratch and the grids);
+//   5. k_mm_verify     output-centric over the C candidates as k_locate_fill is over positions:
+//                      a workgroup owns tiles of MM_T consecutive candidates, finds each one's
+//                      piece by bisecting the tile's slice of the candidate offsets in LDS, reads
+//                      SA[lo + i] and derives the alignment s = SA - b_j.  Alignments that leave
+//                      the text are rejected before any text read.  q and t[s .. s + m) are
+//                      compared 32 chars a step (text_chars32, XOR, popcount of the 2-bit
+//                      differences; the last word masked to m), stopping once the distance
+//                      exceeds k.  The mismatch bits of each step are also tested against the
+//                      regions of the pieces before j: a candidate of piece j is dropped when a
+//                      non-skipped piece j' < j has no mismatch at this alignment (that piece
+//                      reports it), so every alignment is reported once and nothing is sorted;
+//                      one verdict byte per candidate: the distance, or 0xFF;
+//   6. rocprim exclusive scan of the accept flags, k_mm_offsets (a query's candidates are one
+//      contiguous span, so out_off[q] = the scan at the first candidate of piece q (k + 1)) and
+//      k_mm_scatter (out_pos / out_dist, bounded by capacity).  Order is kept: (piece, SA rank).
+//
+// The query words of a compare are packed from the caller's bytes per candidate
+// (pack_query_word: the candidates of a query are neighbours, so its bytes are read from L2).
+// SAS_MM_QWORDS=packed in the environment packs every query once into scratch instead
+// (k_mm_prepack) and reads one 8-B word per step: the verify kernel is then faster on long
+// queries, the whole call slower on every shape measured (the A/B of tools/bench_mismatch.py;
+// DESIGN.md has both figures).
+#include "build_util.hpp"
+
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define MM_BLOCK 256
+#define MM_T 2048          // candidates per tile
+#define MM_PER (MM_T / MM_BLOCK)
+#define MM_SLICE 4096      // candidate offsets of a tile staged in LDS (16 KiB)
+#define MM_MAX_GRID (1u << 20)
+#define MM_MAX_K 15
+#define MM_REJECT 0xFFu
+
+struct MmQueries {
+    const uint8_t* qbytes;
+    const uint64_t* qoff;  // null: fixed-length queries of m chars
+    const uint32_t* qlen;
+    uint32_t m;
+    uint64_t nq;
+    __device__ __forceinline__ uint64_t off(uint64_t q) const { return qoff ? qoff[q] : q * (uint64_t)m; }
+    __device__ __forceinline__ uint32_t len(uint64_t q) const { return qoff ? qlen[q] : m; }
+};
+
+// b_j: the first char of piece j of a query of m chars cut into kp1 pieces
+__device__ __forceinline__ uint32_t mm_piece_start(uint32_t j, uint32_t m, uint32_t kp1) {
+    return (uint32_t)(((uint64_t)j * m) / kp1);
+}
+
+__global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff, uint32_t* __restrict__ plen) {
+    GRID_STRIDE(i, Q.nq * kp1) {
+        const uint64_t q = i / kp1;
+        const uint32_t j = (uint32_t)(i - q * kp1), m = Q.len(q);
+        const uint32_t b0 = mm_piece_start(j, m, kp1), b1 = mm_piece_start(j + 1, m, kp1);
+        poff[i] = Q.off(q) + b0;
+        plen[i] = b1 - b0;
+    }
+}
+
+// One thread per query: skipped seeds and short queries lose their ranges
+__global__ void k_mm_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint64_t* __restrict__ lo,
+                          uint64_t* __restrict__ hi, uint16_t* __restrict__ skip, uint8_t* __restrict__ qflags) {
+    GRID_STRIDE(q, Q.nq) {
+        const bool is_short = Q.len(q) < kp1;  // m <= k
+        uint32_t mask = 0, fl = is_short ? SAS_MM_SHORT : 0u;
+        for (uint32_t j = 0; j < kp1; j++) {
+            const uint64_t i = q * kp1 + j;
+            const uint64_t cnt = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
+            const bool over = !is_short && max_seed_hits && cnt > max_seed_hits;
+            if (over) fl |= SAS_MM_TRUNCATED;
+            if (over || is_short) {
+                mask |= 1u << j;
+                lo[i] = 0;
+                hi[i] = 0;
+            }
+        }
+        skip[q] = (uint16_t)mask;
+        qflags[q] = (uint8_t)fl;
+    }
+}
+
+// words of query q in the packed scratch: ceil(m / 32)
+__global__ void k_mm_wcount(MmQueries Q, uint64_t* __restrict__ woff) {
+    GRID_STRIDE(q, Q.nq + 1) woff[q] = q < Q.nq ? ((uint64_t)Q.len(q) + 31) >> 5 : 0;
+}
+
+__global__ void k_mm_prepack(MmQueries Q, const uint64_t* __restrict__ woff, uint64_t* __restrict__ qw) {
+    uint32_t bad = 0;
+    GRID_STRIDE(q, Q.nq) {
+        const uint32_t m = Q.len(q), nw = (uint32_t)(((uint64_t)m + 31) >> 5);
+        const uint8_t* b = Q.qbytes + Q.off(q);
+        uint64_t* w = qw + woff[q];
+        for (uint32_t j = 0; j < nw; j++) w[j] = pack_query_word(b, m, j, &bad);
+    }
+}
+
+// the last i in [0, np] with off[i] <= v (off[0] = 0): for v below the total a non-empty piece
+__device__ __forceinline__ uint64_t mm_piece_of(const uint64_t* __restrict__ off, uint64_t np, uint64_t v) {
+    uint64_t l = 0, h = np + 1;
+    while (l < h) {
+        const uint64_t mid = (l + h) >> 1;
+        if (off[mid] <= v) l = mid + 1;
+        else h = mid;
+    }
+    return l ? l - 1 : 0;
+}
+
+struct MmArgs {
+    const uint64_t* tw;
+    uint64_t n;
+    const uint8_t* sa;
+    MmQueries Q;
+    uint32_t k;
+    const uint64_t* lo;     // gated first rank per piece
+    const uint64_t* coff;   // candidate offsets, np + 1
+    uint64_t np;            // pieces
+    uint64_t C;             // candidates
+    const uint16_t* skip;   // per query: bit j = piece j is no seed
+    const uint64_t* woff;   // PRE: first packed word per query
+    const uint64_t* qw;     // PRE: packed query words
+    uint8_t* verdict;       // per candidate: distance, or MM_REJECT
+    uint64_t* cpos;         // per accepted candidate: the alignment
+};
+
+// Candidate `c` = occurrence `rank` of piece i at text position pv: the verdict for the
+// alignment s = pv - b_j
+template <bool PRE>
+__device__ __forceinline__ uint32_t mm_verify_one(const MmArgs& a, uint64_t i, uint64_t pv, uint64_t* s_out) {
+    const uint32_t kp1 = a.k + 1;
+    const uint64_t q = i / kp1;
+    const uint32_t j = (uint32_t)(i - q * kp1), m = a.Q.len(q);
+    const uint32_t bj = mm_piece_start(j, m, kp1);
+    if (pv < bj || pv - bj + m > a.n) return MM_REJECT;  // leaves the text: no text read
+    const uint64_t s = pv - bj;
+    *s_out = s;
+    const uint32_t skipm = a.skip[q];
+    const uint8_t* qb = PRE ? nullptr : a.Q.qbytes + a.Q.off(q);
+    const uint64_t* qw = PRE ? a.qw + a.woff[q] : nullptr;
+    uint32_t dist = 0, dirty = 0, jp = 0, jb = 0, je = mm_piece_start(1, m, kp1), bad = 0;
+    for (uint32_t off = 0; off < m; off += 32) {
+        const uint32_t c = m - off < 32 ? m - off : 32;
+        const uint64_t t = text_chars32(a.tw, s + off);
+        const uint64_t w = PRE ? qw[off >> 5] : pack_query_word(qb, m, off >> 5, &bad);
+        const uint64_t x = t ^ w;
+        const uint64_t d = (x | (x >> 1)) & 0x5555555555555555ull & chars_mask(c);  // one bit per differing char
+        dist += (uint32_t)__popcll(d);
+        if (dist > a.k) return MM_REJECT;
+        // the pieces before j that meet chars [off, off + c): a mismatch in one makes it dirty
+        while (jp < j) {
+            const uint32_t r0 = jb > off ? jb - off : 0, r1 = je < off + c ? je - off : c;
+            if (r0 < r1 && (d & chars_mask(r1) & ~chars_mask(r0))) dirty |= 1u << jp;
+            if (je > off + c) break;  // continues in the next word
+            jp++;
+            jb = je;
+            je = mm_piece_start(jp + 1, m, kp1);
+        }
+    }
+    // a non-skipped earlier piece matches exactly here: that piece reports the alignment
+    if (~dirty & ~skipm & ((1u << j) - 1u)) return MM_REJECT;
+    return dist;
+}
+
+template <int W, bool PRE>
+__global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
+    __shared__ uint32_t rel[MM_SLICE];
+    __shared__ uint64_t sh_p[2];
+    const SaView<W> sa{a.sa};
+    const uint32_t tid = threadIdx.x;
+    const uint64_t C = a.C, ntiles = (C + MM_T - 1) / MM_T;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * (uint64_t)MM_T;
+        const uint64_t t1 = t0 + MM_T < C ? t0 + MM_T : C;
+        const uint32_t n_el = (uint32_t)(t1 - t0);
+        // the pieces of the tile's first and last candidate (both non-empty)
+        if (tid < 2) sh_p[tid] = mm_piece_of(a.coff, a.np, tid ? t1 - 1 : t0);
+        __syncthreads();
+        const uint64_t p0 = sh_p[0];
+        uint64_t p1 = sh_p[1];
+        if (p1 < p0) p1 = p0;
+        if (p1 > a.np - 1) p1 = a.np - 1;
+        const uint64_t nps = p1 - p0 + 1;
+        const uint32_t staged = nps <= MM_SLICE ? 1u : 0u;
+        if (staged) {
+            for (uint32_t x = tid; x < (uint32_t)nps; x += MM_BLOCK) {
+                const uint64_t o = a.coff[p0 + x];
+                rel[x] = o <= t0 ? 0u : (o - t0 >= MM_T ? (uint32_t)MM_T : (uint32_t)(o - t0));
+            }
+            __syncthreads();
+        }
+        // element e of the tile belongs to the last piece x in [p0, p1] with coff[x] <= t0 + e
+        uint64_t pi[MM_PER], rk[MM_PER];
+        uint32_t ok[MM_PER];
+#pragma unroll
+        for (int u = 0; u < MM_PER; u++) {
+            const uint32_t e = u * MM_BLOCK + tid;
+            const uint64_t c = t0 + e;
+            ok[u] = e < n_el ? 1u : 0u;
+            pi[u] = rk[u] = 0;
+            if (ok[u]) {
+                uint64_t l = 1, h = nps;
+                if (staged) {
+                    while (l < h) {
+                        const uint64_t mid = (l + h) >> 1;
+                        if (rel[mid] <= e) l = mid + 1;
+                        else h = mid;
+                    }
+                } else {
+                    while (l < h) {
+                        const uint64_t mid = (l + h) >> 1;
+                        if (a.coff[p0 + mid] <= c) l = mid + 1;
+                        else h = mid;
+                    }
+                }
+                pi[u] = p0 + l - 1;
+                const uint64_t o = a.coff[pi[u]];
+                rk[u] = a.lo[pi[u]] + (c - o);
+                ok[u] = (o <= c && c < a.coff[pi[u] + 1] && rk[u] < a.n) ? 1u : 0u;
+            }
+        }
+        uint64_t pv[MM_PER];  // all of a thread's SA reads are issued before the first is used
+#pragma unroll
+        for (int u = 0; u < MM_PER; u++) pv[u] = ok[u] ? sa[rk[u]] : 0;
+#pragma unroll
+        for (int u = 0; u < MM_PER; u++) {
+            const uint32_t e = u * MM_BLOCK + tid;
+            if (e < n_el) {
+                uint64_t s = 0;
+                const uint32_t v = ok[u] ? mm_verify_one<PRE>(a, pi[u], pv[u], &s) : MM_REJECT;
+                a.verdict[t0 + e] = (uint8_t)v;
+                if (v != MM_REJECT) a.cpos[t0 + e] = s;
+            }
+        }
+        __syncthreads();  // rel and sh_p are rewritten by the next tile
+    }
+}
+
+struct MmAccept {
+    __device__ __host__ uint64_t operator()(uint8_t v) const { return v != MM_REJECT ? 1ull : 0ull; }
+};
+
+// out_off[q] = accepted candidates before the first candidate of query q's first piece
+__global__ void k_mm_offsets(const uint64_t* __restrict__ coff, const uint64_t* __restrict__ scan, uint64_t nq,
+                             uint32_t kp1, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_total) {
+    GRID_STRIDE(q, nq + 1) {
+        const uint64_t v = scan[coff[q * kp1]];
+        out_off[q] = v;
+        if (q == nq && out_total) *out_total = v;
+    }
+}
+
+template <bool U32>
+__global__ void k_mm_scatter(const uint8_t* __restrict__ verdict, const uint64_t* __restrict__ scan,
+                             const uint64_t* __restrict__ cpos, uint64_t C, void* __restrict__ out_pos,
+                             uint8_t* __restrict__ out_dist, uint64_t capacity) {
+    GRID_STRIDE(c, C) {
+        const uint32_t v = verdict[c];
+        if (v == MM_REJECT) continue;
+        const uint64_t o = scan[c];
+        if (o >= capacity) continue;
+        if (U32) static_cast<uint32_t*>(out_pos)[o] = (uint32_t)cpos[c];
+        else static_cast<uint64_t*>(out_pos)[o] = cpos[c];
+        if (out_dist) out_dist[o] = (uint8_t)v;
+    }
+}
+
+struct MmPoolBuf {  // stream-ordered scratch from the index's pool
+    void* p = nullptr;
+    hipStream_t st = nullptr;
+    ~MmPoolBuf() { if (p) (void)hipFreeAsync(p, st); }
+    template <class T> T* as() { return static_cast<T*>(p); }
+    int alloc(hipMemPool_t pool, size_t bytes, hipStream_t s) {
+        st = s;
+        HIP_TRY(hipMallocFromPoolAsync(&p, bytes ? bytes : 8, pool, s));
+        return 0;
+    }
+};
+
+static int mm_scan(hipMemPool_t pool, hipStream_t st, const uint8_t* verdict, uint64_t* scan, uint64_t count) {
+    auto in = rocprim::make_transform_iterator(verdict, MmAccept{});
+    size_t tbytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, in, scan, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
+                                    st));
+    MmPoolBuf tmp;
+    TRY(tmp.alloc(pool, tbytes, st));
+    HIP_TRY(rocprim::exclusive_scan(tmp.p, tbytes, in, scan, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
+                                    st));
+    return 0;
+}
+
+static int mm_scan_u64(hipMemPool_t pool, hipStream_t st, uint64_t* v, uint64_t count) {
+    size_t tbytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, v, v, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(), st));
+    MmPoolBuf tmp;
+    TRY(tmp.alloc(pool, tbytes, st));
+    HIP_TRY(rocprim::exclusive_scan(tmp.p, tbytes, v, v, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(), st));
+    return 0;
+}
+
+// SAS_MM_QWORDS=packed: pack every query once into scratch (the A/B knob; read at every call,
+// so one process can measure both)
+static bool mm_prepacked() {
+    const char* e = getenv("SAS_MM_QWORDS");
+    return e && strcmp(e, "packed") == 0;
+}
+
+// SAS_MM_TIMING=1: the verify kernel of every call is timed with HIP events (synchronises);
+// sas_locate_mismatch_verify_ms returns the calling thread's last figure
+static thread_local double mm_last_verify_ms = -1.0;
+static thread_local uint64_t mm_last_candidates = 0;
+static bool mm_timing() {
+    const char* e = getenv("SAS_MM_TIMING");
+    return e && e[0] == '1';
+}
+
+extern "C" double sas_locate_mismatch_verify_ms(uint64_t* candidates) {
+    if (candidates) *candidates = mm_last_candidates;
+    return mm_last_verify_ms;
+}
+
+// Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
+struct MmState {
+    hipMemPool_t pool = nullptr;
+    MmPoolBuf poff, plen, lohi, coff, skip, qfl, woff, qw, verdict, cpos, scan;
+    uint64_t C = 0;
+};
+
+// All arrays on the device (out_total may be null).  The one host read: the candidate total
+static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off,
+                      uint8_t* out_qflags, uint64_t* out_total, hipStream_t st, uint32_t flags, MmState& s) {
+    const uint32_t kp1 = k + 1;
+    const uint64_t nq = Q.nq, np = nq * kp1;
+    TRY(sas_scratch_pool(x, &s.pool));
+    TRY(s.poff.alloc(s.pool, np * 8, st));
+    TRY(s.plen.alloc(s.pool, np * 4, st));
+    TRY(s.lohi.alloc(s.pool, np * 16, st));
+    TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
+    TRY(s.skip.alloc(s.pool, nq * 2, st));
+    if (!out_qflags) {
+        TRY(s.qfl.alloc(s.pool, nq, st));
+        out_qflags = s.qfl.as<uint8_t>();
+    }
+    uint64_t* lo = s.lohi.as<uint64_t>();
+    uint64_t* hi = lo + np;
+    const unsigned cap_grid = (unsigned)x->num_cus * 8;
+    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    hipLaunchKernelGGL(k_mm_pieces, grid(np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(), s.plen.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
+    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, lo, hi, st, rflags));
+    hipLaunchKernelGGL(k_mm_gate, grid(nq), dim3(256), 0, st, Q, kp1, max_seed_hits, lo, hi, s.skip.as<uint16_t>(),
+                       out_qflags);
+    HIP_TRY(hipGetLastError());
+    TRY(sas_locate_offsets(x, lo, hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS));
+    // SAS_MM_QWORDS=packed: ceil(m / 32) words per query; for ragged queries their total is read
+    // back together with the candidate total (one synchronisation)
+    const bool pre = mm_prepacked();
+    uint64_t words = nq * (((uint64_t)Q.m + 31) >> 5);
+    if (pre) {
+        TRY(s.woff.alloc(s.pool, (nq + 1) * 8, st));
+        hipLaunchKernelGGL(k_mm_wcount, grid(nq + 1), dim3(256), 0, st, Q, s.woff.as<uint64_t>());
+        HIP_TRY(hipGetLastError());
+        TRY(mm_scan_u64(s.pool, st, s.woff.as<uint64_t>(), nq + 1));
+        if (Q.qoff) HIP_TRY(hipMemcpyAsync(&words, s.woff.as<uint64_t>() + nq, 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(&s.C, s.coff.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t C = s.C;
+    mm_last_candidates = C;
+    mm_last_verify_ms = -1.0;
+    if (C == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
+        if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
+        return 0;
+    }
+    if (pre) {
+        TRY(s.qw.alloc(s.pool, words * 8, st));
+        hipLaunchKernelGGL(k_mm_prepack, grid(nq), dim3(256), 0, st, Q, s.woff.as<uint64_t>(), s.qw.as<uint64_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    TRY(s.verdict.alloc(s.pool, C + 1, st));
+    TRY(s.cpos.alloc(s.pool, C * 8, st));
+    TRY(s.scan.alloc(s.pool, (C + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(s.verdict.as<uint8_t>() + C, MM_REJECT, 1, st));
+    MmArgs a{};
+    a.tw = x->text_w;
+    a.n = x->n;
+    a.sa = x->sa;
+    a.Q = Q;
+    a.k = k;
+    a.lo = lo;
+    a.coff = s.coff.as<uint64_t>();
+    a.np = np;
+    a.C = C;
+    a.skip = s.skip.as<uint16_t>();
+    a.woff = s.woff.as<uint64_t>();
+    a.qw = s.qw.as<uint64_t>();
+    a.verdict = s.verdict.as<uint8_t>();
+    a.cpos = s.cpos.as<uint64_t>();
+    uint64_t blocks = (C + MM_T - 1) / MM_T;
+    if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
+    const dim3 vgrid((unsigned)blocks);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timing = mm_timing();
+    if (timing) {
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+    }
+    if (x->sa_w == 5) {
+        if (pre) hipLaunchKernelGGL((k_mm_verify<5, true>), vgrid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_mm_verify<5, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
+    } else {
+        if (pre) hipLaunchKernelGGL((k_mm_verify<4, true>), vgrid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_mm_verify<4, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
+    }
+    HIP_TRY(hipGetLastError());
+    if (timing) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        mm_last_verify_ms = ms;
+    }
+    TRY(mm_scan(s.pool, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(), C + 1));
+    hipLaunchKernelGGL(k_mm_offsets, grid(nq + 1), dim3(256), 0, st, s.coff.as<uint64_t>(), s.scan.as<uint64_t>(), nq,
+                       kp1, out_off, out_total);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int mm_scatter(const sas_index* x, MmState& s, void* out_pos, uint8_t* out_dist, uint64_t capacity,
+                      hipStream_t st, uint32_t flags) {
+    if (s.C == 0 || capacity == 0) return 0;
+    const dim3 grid(std::min(grid_for(s.C), (unsigned)x->num_cus * 8));
+    if (flags & SAS_LOCATE_U32)
+        hipLaunchKernelGGL(k_mm_scatter<true>, grid, dim3(256), 0, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(),
+                           s.cpos.as<uint64_t>(), s.C, out_pos, out_dist, capacity);
+    else
+        hipLaunchKernelGGL(k_mm_scatter<false>, grid, dim3(256), 0, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(),
+                           s.cpos.as<uint64_t>(), s.C, out_pos, out_dist, capacity);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int mismatch_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
+                         const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
+                         uint64_t* out_off, void* out_pos, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
+                         uint64_t* out_total, void* stream, uint32_t flags) {
+    const std::string w(fn);
+    if (!x) SAS_FAIL(EINVAL, w + ": null index");
+    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
+    if (x->tag_lines || x->sa_w == 8)
+        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
+    if (x->rank_lo != 0 || x->sa_n != x->n)
+        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
+    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
+    // the range search's own requirements (its error is passed on)
+    TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
+    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
+    if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_pos) ||
+        (!dev && !out_total))
+        SAS_FAIL(EINVAL, w + ": null argument");
+    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
+        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
+    HIP_TRY(hipSetDevice(x->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (nq == 0) {
+        if (dev) {
+            HIP_TRY(hipMemsetAsync(out_off, 0, 8, st));
+            if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
+        } else {
+            out_off[0] = 0;
+            *out_total = 0;
+        }
+        return 0;
+    }
+    MmState s;
+    if (dev) {
+        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
+        TRY(mm_prepare(x, Q, k, max_seed_hits, out_off, out_qflags, out_total, st, flags, s));
+        return mm_scatter(x, s, out_pos, out_dist, capacity, st, flags);
+    }
+    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
+    uint64_t span = nq * (uint64_t)m;
+    if (ragged) {
+        span = 0;
+        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
+    }
+    DevBuf dq, dqoff, dqlen, doff, dfl, dtot, dpos, ddist;
+    TRY(dq.alloc(span + 64, "mismatch queries"));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
+    if (ragged) {
+        TRY(dqoff.alloc(nq * 8, "mismatch offsets"));
+        TRY(dqlen.alloc(nq * 4, "mismatch lengths"));
+        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
+    }
+    TRY(doff.alloc((nq + 1) * 8, "mismatch result offsets"));
+    TRY(dfl.alloc(nq, "mismatch query flags"));
+    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
+    TRY(mm_prepare(x, Q, k, max_seed_hits, doff.as<uint64_t>(), dfl.as<uint8_t>(), nullptr, st, flags | SAS_VALIDATE,
+                   s));
+    HIP_TRY(hipMemcpyAsync(out_off, doff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (out_qflags) HIP_TRY(hipMemcpyAsync(out_qflags, dfl.p, nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t total = out_off[nq];
+    *out_total = total;
+    if (total > capacity)
+        SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " positions, capacity " + std::to_string(capacity) +
+                             " (size out_pos from *out_total and call again)");
+    if (total == 0) return 0;
+    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8;
+    TRY(dpos.alloc(total * esz, "mismatch positions"));
+    if (out_dist) TRY(ddist.alloc(total, "mismatch distances"));
+    TRY(mm_scatter(x, s, dpos.p, out_dist ? ddist.as<uint8_t>() : nullptr, total, st, flags));
+    HIP_TRY(hipMemcpyAsync(out_pos, dpos.p, total * esz, hipMemcpyDeviceToHost, st));
+    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, ddist.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int sas_locate_mismatch(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff,
+                                   const uint32_t* qlen, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
+                                   uint64_t* out_off, void* out_pos, uint8_t* out_dist, uint8_t* out_qflags,
+                                   uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
+    return mismatch_impl("sas_locate_mismatch", x, qbytes, true, qoff, qlen, 0, nq, k, max_seed_hits, out_off, out_pos,
+                         out_dist, out_qflags, capacity, out_total, stream, flags);
+}
+
+extern "C" int sas_locate_mismatch_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                                         uint64_t max_seed_hits, uint64_t* out_off, void* out_pos, uint8_t* out_dist,
+                                         uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
+                                         uint32_t flags) {
+    return mismatch_impl("sas_locate_mismatch_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, max_seed_hits,
+                         out_off, out_pos, out_dist, out_qflags, capacity, out_total, stream, flags);
+}

@@ -709,6 +709,82 @@ class SaNaive:
         plen = int(pattern.numel() if _is_cuda(pattern) else len(pattern))
         return self._match("stats", pattern, None, None, int(max_len), plen, ranges, stream, flags)
 
+    # -- k-mismatch locate (sas_locate_mismatch*)
+    def _locate_mismatch(self, qbytes, qoff, qlen, m, nq, k, max_seed_hits, u32, dist, stream, out, capacity, flags):
+        L = lib()
+
+        def call(off, pos, dst, qfl, cap, total, st, fl):
+            tail = (int(k), int(max_seed_hits), _ptr(off), _ptr(pos), _ptr(dst), _ptr(qfl), int(cap), total, st, fl)
+            if qoff is not None:
+                return L.sas_locate_mismatch(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *tail)
+            return L.sas_locate_mismatch_fixed(self._h, _ptr(qbytes), m, nq, *tail)
+
+        if _is_cuda(qbytes):
+            import torch
+            d = qbytes.device
+            dt = torch.int32 if u32 else torch.int64
+            st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+            fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+            off = torch.empty(nq + 1, dtype=torch.int64, device=d)
+            qfl = torch.empty(nq, dtype=torch.uint8, device=d)
+            total = None
+            if out is None and capacity is None:  # a sizing call, one read of the total, the real call
+                check(call(off, None, None, qfl, 0, None, st, fl))
+                capacity = total = int(off[nq].item())
+            if out is None:
+                out = torch.empty(max(int(capacity), 1), dtype=dt, device=d)
+            elif not _is_cuda(out) or out.dtype != dt or not out.is_contiguous():
+                raise ValueError(f"locate_mismatch: out must be a contiguous CUDA {dt} tensor")
+            capacity = out.numel() if capacity is None else capacity
+            if capacity > out.numel():
+                raise ValueError("locate_mismatch: capacity exceeds out")
+            dst = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=d) if dist else None
+            if total != 0:
+                check(call(off, out, dst, qfl, capacity, None, st, fl))
+            if total is not None:
+                out, dst = out[:total], (dst[:total] if dist else None)
+            return off, out, dst, qfl
+        qbytes = _as_u8(qbytes)
+        fl = flags | (_lib.SAS_LOCATE_U32 if u32 else 0)
+        off = np.zeros(nq + 1, np.uint64)
+        qfl = np.zeros(max(nq, 1), np.uint8)
+        total = C.c_uint64(0)
+        rc = call(off, None, None, qfl, 0, C.byref(total), stream, fl)  # the sizing call
+        if rc not in (0, errno.ENOSPC):
+            check(rc)
+        pos = np.zeros(max(total.value, 1), np.uint32 if u32 else np.uint64)
+        dst = np.zeros(max(total.value, 1), np.uint8) if dist else None
+        if total.value:
+            check(call(off, pos, dst, qfl, total.value, C.byref(total), stream, fl))
+        return off, pos[:total.value], (dst[:total.value] if dist else None), qfl[:nq]
+
+    def locate_mismatch(self, qbytes, qoff, qlen, k: int, max_seed_hits: int = 0, u32: bool = False,
+                        dist: bool = True, stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """Every alignment of every ragged query qbytes[qoff[i] : qoff[i] + qlen[i]] with at most
+        k substituted chars (sas_locate_mismatch): (off, pos, dist, qflags).  Query i's alignments
+        are pos[off[i] : off[i + 1]], dist their Hamming distances (None with dist=False), qflags[i]
+        a mask of SAS_MM_TRUNCATED (a seed occurred more than max_seed_hits times and was skipped;
+        0: no limit) and SAS_MM_SHORT (len <= k: no result).  numpy in -> numpy out (a sizing
+        call, then the real one); torch CUDA in -> CUDA out: with out / capacity one call that
+        writes nothing at or past the capacity (the caller checks off[nq]), otherwise a sizing
+        call first."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._locate_mismatch(qbytes, qoff, qlen, 0, nq, k, max_seed_hits, u32, dist, stream, out, capacity,
+                                     flags)
+
+    def locate_mismatch_fixed(self, qbytes, m: int, k: int, max_seed_hits: int = 0, u32: bool = False,
+                              dist: bool = True, stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """locate_mismatch for fixed-length queries qbytes[i*m : (i+1)*m] (sas_locate_mismatch_fixed)."""
+        if m <= 0:
+            raise ValueError("use locate_mismatch for empty queries")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._locate_mismatch(qbytes, None, None, int(m), nq, k, max_seed_hits, u32, dist, stream, out,
+                                     capacity, flags)
+
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
         kn, cn = C.c_double(0), C.c_double(0)
