@@ -560,6 +560,69 @@ int sas_locate_mismatch_fixed(const sas_index* index, const uint8_t* qbytes, uin
  * calling thread's last figure in ms (< 0: none) and the candidates it verified. */
 double sas_locate_mismatch_verify_ms(uint64_t* candidates);
 
+/* k-difference locate (unit-cost edit distance: a substitution, an insertion and a deletion
+ * cost 1 each): Sellers' problem, by seed and verify.  For a query q of m chars and the text
+ * t of n chars let D(e) = min over 0 <= s <= e of ed(q, t[s .. e)), defined for every end
+ * position e in [0, n].  Nothing behind the text end takes part: the zero padding of the
+ * packed text is not text.  The k-difference answer of q is every e with D(e) <= k, each
+ * reported once with its distance D(e), in ascending order of e.  The neighbouring ends of
+ * one alignment are all reported: an exact occurrence ending at e also gives e - j and e + j
+ * with distance j for every j <= k, wherever nothing better ends there.  Where an alignment
+ * starts and its edit script are not reported.
+ * The query is cut as for sas_locate_mismatch, into k + 1 pieces, piece j = chars [b_j,
+ * b_{j+1}) with b_j = floor(j m / (k + 1)).  An alignment with at most k edits leaves one piece
+ * untouched, which then occurs exactly at some text position pv; with s0 = pv - b_j (signed)
+ * the alignment ends in [s0 + m - k, s0 + m + k].  Every occurrence of a piece (one
+ * sas_search_range over all pieces) is a candidate, and one kernel runs Myers' bit-vector
+ * algorithm, free start, over the window t[max(0, s0 - 2k) .. min(n, s0 + m + k)) of each: every
+ * alignment of cost <= k that ends in the candidate's interval starts inside that window, so
+ * D(e) capped at k + 1 is the same whichever candidate computes it.  The ends that several
+ * candidates propose are sorted and reported once.
+ *   - a piece that occurs more than max_seed_hits times in the text (max_seed_hits == 0: no
+ *     limit) is skipped as a seed and its query flagged SAS_ED_TRUNCATED; the query's answer
+ *     is then exactly {e : D(e) <= k and some occurrence pv of a non-skipped piece j has
+ *     |e - (pv - b_j + m)| <= k};
+ *   - a query with m <= k (the empty query at every k) gets no result and SAS_ED_SHORT;
+ *   - a query with m > SAS_ED_MAX_M gets no result, no seeds and SAS_ED_LONG (a per-query
+ *     flag, so that one long query does not fail a ragged batch);
+ *   - an unflagged query gets the complete k-difference answer.
+ * Results in CSR form: out_off[0..nq] (u64), out_end (u64, or u32 with SAS_LOCATE_U32, which
+ * needs n < 2^32: EINVAL otherwise), out_dist (one byte per end: D(e); may be NULL) and
+ * out_qflags (one byte per query: SAS_ED_*; may be NULL).  k is 0..15 (EINVAL above).  Flags:
+ * SAS_DEVICE_PTRS, SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE.  Needs what
+ * sas_search_range needs (its error is returned otherwise) on a whole index (no shard, no
+ * part) with a u32 or packed 40-bit SA array; SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES indexes
+ * return ENOTSUP.  The proposals are sorted by a 64-bit key (query, end): if the bits of nq - 1
+ * and of n together exceed 64 the call returns EINVAL and asks to split the batch.
+ * With host pointers: synchronous, bytes always validated; *out_total is always set, out_off
+ * and out_qflags always filled; if the total exceeds `capacity` nothing is copied to out_end /
+ * out_dist and the call returns ENOSPC (out_end == NULL, capacity == 0 is the sizing call).
+ * With SAS_DEVICE_PTRS: scratch from the index's stream-ordered pool; nothing at or past
+ * `capacity` is written; out_total (device, may be NULL) = out_off[nq], which the caller
+ * checks against `capacity` afterwards.  The call synchronises on `stream` TWICE: to read the
+ * number of candidates (the occurrences of all seeds; it sizes the candidate scratch and the
+ * grids) and the number of proposed ends (it sizes the sort).  Nothing else synchronises
+ * unless SAS_VALIDATE is set. */
+#define SAS_ED_TRUNCATED 1u /* out_qflags: a seed was skipped (more than max_seed_hits hits) */
+#define SAS_ED_SHORT     2u /* out_qflags: m <= k, no result                                  */
+#define SAS_ED_LONG      4u /* out_qflags: m > SAS_ED_MAX_M, no result                        */
+#define SAS_ED_MAX_M     256u
+int sas_locate_edit(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                    uint64_t nq, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off, void* out_end,
+                    uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
+                    void* stream, uint32_t flags);
+/* sas_locate_edit for fixed-length queries qbytes[k*m .. (k+1)*m). */
+int sas_locate_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                          uint64_t max_seed_hits, uint64_t* out_off, void* out_end, uint8_t* out_dist,
+                          uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
+                          uint32_t flags);
+/* Timing helpers for benches: with SAS_ED_TIMING=1 in the environment every sas_locate_edit*
+ * call times its verify kernel, and the de-duplication from the first proposal written to the
+ * offsets, with HIP events (and synchronises to do so); these return the calling thread's last
+ * figures in ms (< 0: none), with the candidates verified and the ends proposed. */
+double sas_locate_edit_verify_ms(uint64_t* candidates);
+double sas_locate_edit_dedup_ms(uint64_t* proposals);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

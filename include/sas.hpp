@@ -302,6 +302,44 @@ class SaNaive {
         return r;
     }
 
+    /* CSR result of locate_edit: query k's end positions are end[off[k] .. off[k+1]), ascending,
+     * with D(e) (the least edit distance of the query to a text substring ending at e) in dist;
+     * qflags[k] is a mask of SAS_ED_TRUNCATED, SAS_ED_SHORT and SAS_ED_LONG */
+    struct Edited {
+        std::vector<uint64_t> off, end;
+        std::vector<uint8_t> dist, qflags;
+    };
+
+    /* every end position of every query within edit distance k (substitutions, insertions and
+     * deletions), in one call (sas_locate_edit: seed and verify on the GPU); a seed that occurs
+     * more than max_seed_hits times is skipped (0: no limit) */
+    Edited locate_edit(const std::vector<Seq>& qs, uint32_t k, uint64_t max_seed_hits = 0, uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Edited r;
+        r.off.assign(qs.size() + 1, 0);
+        r.qflags.assign(qs.size(), 0);
+        uint64_t total = 0;
+        /* the sizing call (ENOSPC unless nothing is within k), then the real one */
+        const int rc = sas_locate_edit(h_, bytes.data(), qoff.data(), len.data(), qs.size(), k, max_seed_hits,
+                                       r.off.data(), nullptr, nullptr, r.qflags.data(), 0, &total, nullptr, flags);
+        if (rc != ENOSPC) check(rc);
+        r.end.resize(total);
+        r.dist.resize(total);
+        if (total)
+            check(sas_locate_edit(h_, bytes.data(), qoff.data(), len.data(), qs.size(), k, max_seed_hits,
+                                  r.off.data(), r.end.data(), r.dist.data(), r.qflags.data(), total, &total, nullptr,
+                                  flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are

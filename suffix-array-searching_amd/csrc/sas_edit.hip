@@ -1,0 +1,568 @@
+// sas_edit.hip -- k-difference locate (unit-cost edit distance) by seed and verify (sas.h:
+// sas_locate_edit, sas_locate_edit_fixed).
+//
+// For a query q of m chars, D(e) = min over s <= e of ed(q, t[s .. e)) is defined for every
+// end e in [0, n]; the answer is every e with D(e) <= k (Sellers' problem).  The query is cut
+// as for sas_locate_mismatch, into k + 1 pieces with b_j = floor(j m / (k + 1)): an alignment
+// with at most k edits leaves one piece untouched, so that piece occurs exactly at some text
+// position pv, and with s0 = pv - b_j (signed) the alignment ends in [s0 + m - k, s0 + m + k].
+// A candidate is one occurrence of one piece:
+//
+//   1. k_mm_pieces, 2. sas_search_range, 4. sas_locate_offsets: as in sas_mismatch.hip;
+//   3. k_ed_gate       empties the range of every piece that occurs more than max_seed_hits
+//                      times, and every piece of a query with m <= k or m > SAS_ED_MAX_M; writes
+//                      the per-query flags;
+//   5. k_ed_verify     output-centric over the C candidates (mm_tile_candidates).  Per candidate
+//                      Myers' bit-vector algorithm in its search form (free start: the
+//                      horizontal delta into row 0 is 0; the score starts at m and follows the
+//                      Ph / Mh bit of row m - 1) over the columns of the window
+//                      t[max(0, s0 - 2k) .. min(n, s0 + m + k)).  Every alignment of cost <= k
+//                      that ends in the candidate's interval starts at or after s0 - 2k, so the
+//                      score there, capped at k + 1, is D(e) itself, whichever candidate
+//                      computes it.  The query is two bit planes per 64 rows (the low and the
+//                      high bit of each char); the match vector of a text char c is
+//                      ~(L ^ -(c & 1)) & ~(H ^ -(c >> 1)), masked to m: no table indexed by the
+//                      char.  The number of 64-row words is a template parameter (1, 2 or 4;
+//                      ragged batches switch per thread), so the planes and Pv / Mv stay in
+//                      named registers.  Text chars come 32 columns per text_chars32, never from
+//                      a column >= n.  A candidate stops once score - columns left > k (the
+//                      score falls by at most 1 per column: nothing later can be reported).
+//                      Output per candidate: a mask of the accepted ends (bit i: e = s0 + m - k
+//                      + i), their distances 4 bits each, and the sort key of bit 0;
+//   6. de-duplication  the same end is proposed by several pieces and, in repeats, by several
+//                      occurrences: popcount of the masks, exclusive scan, the host reads the
+//                      proposal total P (the call's second read-back: it sizes the sort), k_ed_emit
+//                      writes one (key, dist) pair per proposal with key = (query << ebits) | e,
+//                      rocprim::radix_sort_pairs over the ebits + qbits significant bits, an
+//                      exclusive scan of "first of its run of equal keys", k_ed_offsets
+//                      (out_off[q] = unique keys below query q, by bisection) and k_ed_scatter
+//                      (out_end / out_dist, bounded by capacity).  Equal keys carry equal
+//                      distances, so which duplicate is kept does not matter.
+#include "seed_verify.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+// One thread per query: skipped seeds, short and long queries lose their ranges
+__global__ void k_ed_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint64_t* __restrict__ lo,
+                          uint64_t* __restrict__ hi, uint8_t* __restrict__ qflags) {
+    GRID_STRIDE(q, Q.nq) {
+        const uint32_t m = Q.len(q);
+        uint32_t fl = m < kp1 ? SAS_ED_SHORT : (m > SAS_ED_MAX_M ? SAS_ED_LONG : 0u);
+        const bool none = fl != 0;
+        for (uint32_t j = 0; j < kp1; j++) {
+            const uint64_t i = q * kp1 + j;
+            const uint64_t cnt = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
+            const bool over = !none && max_seed_hits && cnt > max_seed_hits;
+            if (over) fl |= SAS_ED_TRUNCATED;
+            if (over || none) {
+                lo[i] = 0;
+                hi[i] = 0;
+            }
+        }
+        qflags[q] = (uint8_t)fl;
+    }
+}
+
+struct EdArgs {
+    const uint64_t* tw;
+    uint64_t n;
+    const uint8_t* sa;
+    MmQueries Q;
+    uint32_t k;
+    uint32_t ebits;         // key = (query << ebits) | end
+    const uint64_t* lo;     // gated first rank per piece
+    const uint64_t* coff;   // candidate offsets, np + 1
+    uint64_t np;            // pieces
+    uint64_t C;             // candidates
+    uint32_t* mask;         // per candidate: bit i = the end s0 + m - k + i is accepted
+    uint64_t* kbase;        // per candidate: the key of bit 0 (modulo 2^64: s0 + m - k may be < 0)
+    ulonglong2* dists;      // per candidate: the distance of bit i in bits [4 i, 4 i + 4)
+};
+
+// even bits of x (bit 2 p -> bit p)
+__device__ __forceinline__ uint32_t ed_even_bits(uint64_t x) {
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
+    return (uint32_t)x;
+}
+
+// The bit planes of query chars [32 j, 32 j + 32): bit r of lo / hi = the low / high bit of char
+// 32 j + r (pack_query_word has char r in bits 63 - 2 r, 62 - 2 r; zero behind m)
+__device__ __forceinline__ void ed_planes32(const uint8_t* __restrict__ qb, uint32_t m, uint32_t j, uint32_t* lo,
+                                            uint32_t* hi) {
+    uint32_t bad = 0;
+    const uint64_t w = pack_query_word(qb, m, j, &bad);
+    *lo = __brev(ed_even_bits(w));
+    *hi = __brev(ed_even_bits(w >> 1));
+}
+
+// Candidate = an occurrence of piece i at text position pv.  NW words of 64 rows (m <= 64 NW)
+template <int NW>
+__device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64_t s0,
+                                              const uint8_t* __restrict__ qb, uint32_t* mask_out, uint64_t* d0_out,
+                                              uint64_t* d1_out) {
+    const int64_t k = (int64_t)a.k, n = (int64_t)a.n;
+    const int64_t w0 = s0 - 2 * k > 0 ? s0 - 2 * k : 0;             // the window's columns [w0, w1)
+    const int64_t w1 = s0 + m + k < n ? s0 + (int64_t)m + k : n;
+    const int64_t e0 = s0 + (int64_t)m - k;                         // the end of bit 0
+    uint32_t mask = 0;
+    uint64_t d0 = 0, d1 = 0;
+    uint64_t L[NW], H[NW], V[NW], Pv[NW], Mv[NW];
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        uint32_t l0, h0, l1, h1;
+        ed_planes32(qb, m, 2 * w, &l0, &h0);
+        ed_planes32(qb, m, 2 * w + 1, &l1, &h1);
+        L[w] = ((uint64_t)l1 << 32) | l0;
+        H[w] = ((uint64_t)h1 << 32) | h0;
+        const uint32_t rows = m > 64u * w ? m - 64u * w : 0u;       // rows of the query in this word
+        V[w] = rows >= 64 ? ~0ull : ((1ull << rows) - 1ull);
+        Pv[w] = ~0ull;
+        Mv[w] = 0;
+    }
+    const uint32_t lw = (m - 1) >> 6, lb = (m - 1) & 63;            // row m - 1: word and bit
+    int64_t score = m;
+    for (int64_t col = w0; col < w1; col += 32) {
+        uint64_t tx = text_chars32(a.tw, (uint64_t)col);            // col < w1 <= n
+        const int64_t cend = col + 32 < w1 ? col + 32 : w1;
+        for (int64_t c = col; c < cend; c++, tx <<= 2) {
+            const uint64_t cl = 0ull - ((tx >> 62) & 1ull), ch = 0ull - (tx >> 63);
+            int hin = 0;                                            // free start: 0 into row 0
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                uint64_t Eq = ~(L[w] ^ cl) & ~(H[w] ^ ch) & V[w];
+                const uint64_t Xv = Eq | Mv[w];
+                Eq |= hin < 0 ? 1ull : 0ull;
+                const uint64_t Xh = (((Eq & Pv[w]) + Pv[w]) ^ Pv[w]) | Eq;
+                uint64_t Ph = Mv[w] | ~(Xh | Pv[w]);
+                uint64_t Mh = Pv[w] & Xh;
+                if ((uint32_t)w == lw) score += (int64_t)((Ph >> lb) & 1ull) - (int64_t)((Mh >> lb) & 1ull);
+                const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
+                Ph = (Ph << 1) | (hin > 0 ? 1ull : 0ull);
+                Mh = (Mh << 1) | (hin < 0 ? 1ull : 0ull);
+                Pv[w] = Mh | ~(Xv | Ph);
+                Mv[w] = Ph & Xv;
+                hin = hout;
+            }
+            const int64_t e = c + 1;                                // the score is D of end c + 1
+            if (score <= k && e >= e0) {
+                const uint32_t i = (uint32_t)(e - e0);              // <= 2k: e <= w1 <= s0 + m + k
+                mask |= 1u << i;
+                if (i < 16) d0 |= (uint64_t)score << (4 * i);
+                else d1 |= (uint64_t)score << (4 * (i - 16));
+            }
+            if (score - (w1 - e) > k) {                             // out of reach for every later end
+                col = w1;
+                break;
+            }
+        }
+    }
+    *mask_out = mask;
+    *d0_out = d0;
+    *d1_out = d1;
+}
+
+// NW: 1, 2, 4 words of 64 rows for every query of the batch (fixed length), 0: by each query's m
+template <int W, int NW>
+__global__ __launch_bounds__(MM_BLOCK) void k_ed_verify(EdArgs a) {
+    __shared__ uint32_t rel[MM_SLICE];
+    __shared__ uint64_t sh_p[2];
+    const SaView<W> sa{a.sa};
+    const uint32_t tid = threadIdx.x, kp1 = a.k + 1;
+    const uint64_t C = a.C, ntiles = (C + MM_T - 1) / MM_T;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * (uint64_t)MM_T;
+        const uint64_t t1 = t0 + MM_T < C ? t0 + MM_T : C;
+        const uint32_t n_el = (uint32_t)(t1 - t0);
+        uint64_t pi[MM_PER], pv[MM_PER];
+        uint32_t ok[MM_PER];
+        mm_tile_candidates(sa, a.coff, a.lo, a.np, a.n, t0, n_el, rel, sh_p, pi, pv, ok);
+#pragma unroll
+        for (int u = 0; u < MM_PER; u++) {
+            const uint32_t e = u * MM_BLOCK + tid;
+            if (e < n_el) {
+                uint32_t mask = 0;
+                uint64_t d0 = 0, d1 = 0, kb = 0;
+                if (ok[u]) {
+                    const uint64_t q = pi[u] / kp1;
+                    const uint32_t j = (uint32_t)(pi[u] - q * kp1), m = a.Q.len(q);
+                    const int64_t s0 = (int64_t)pv[u] - (int64_t)mm_piece_start(j, m, kp1);
+                    const uint8_t* qb = a.Q.qbytes + a.Q.off(q);
+                    kb = (q << a.ebits) + (uint64_t)(s0 + (int64_t)m - (int64_t)a.k);
+                    if (m >= kp1 && m <= SAS_ED_MAX_M) {  // gated already: a guard for the word count
+                        if (NW == 1 || (NW == 0 && m <= 64)) ed_verify_one<1>(a, m, s0, qb, &mask, &d0, &d1);
+                        else if (NW == 2 || (NW == 0 && m <= 128)) ed_verify_one<2>(a, m, s0, qb, &mask, &d0, &d1);
+                        else ed_verify_one<4>(a, m, s0, qb, &mask, &d0, &d1);
+                    }
+                }
+                a.mask[t0 + e] = mask;
+                a.kbase[t0 + e] = kb;
+                a.dists[t0 + e] = make_ulonglong2(d0, d1);
+            }
+        }
+        __syncthreads();  // rel and sh_p are rewritten by the next tile
+    }
+}
+
+struct EdPopcount {
+    __device__ __host__ uint64_t operator()(uint32_t v) const { return (uint64_t)__builtin_popcount(v); }
+};
+
+// One (key, dist) pair per accepted end of every candidate, at the scan of the mask popcounts
+__global__ void k_ed_emit(const uint32_t* __restrict__ mask, const uint64_t* __restrict__ kbase,
+                          const ulonglong2* __restrict__ dists, const uint64_t* __restrict__ pscan, uint64_t C,
+                          uint64_t* __restrict__ keys, uint8_t* __restrict__ vals) {
+    GRID_STRIDE(c, C) {
+        uint32_t mk = mask[c];
+        if (!mk) continue;
+        const uint64_t kb = kbase[c];
+        const ulonglong2 d = dists[c];
+        uint64_t o = pscan[c];
+        while (mk) {
+            const uint32_t i = (uint32_t)__builtin_ctz(mk);
+            mk &= mk - 1;
+            keys[o] = kb + i;
+            vals[o] = (uint8_t)(((i < 16 ? d.x >> (4 * i) : d.y >> (4 * (i - 16)))) & 15ull);
+            o++;
+        }
+    }
+}
+
+// 1 for the first of each run of equal keys in the sorted proposals, 0 at and past P
+struct EdFirst {
+    const uint64_t* keys;
+    uint64_t P;
+    __device__ __host__ uint64_t operator()(uint64_t p) const {
+        return p < P && (p == 0 || keys[p] != keys[p - 1]) ? 1ull : 0ull;
+    }
+};
+
+// out_off[q] = unique keys below (q << ebits): uscan at the first proposal of a query >= q
+__global__ void k_ed_offsets(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ uscan, uint64_t P,
+                             uint64_t nq, uint32_t ebits, uint64_t* __restrict__ out_off,
+                             uint64_t* __restrict__ out_total) {
+    GRID_STRIDE(q, nq + 1) {
+        uint64_t l = 0, h = P;
+        while (l < h) {
+            const uint64_t mid = (l + h) >> 1;
+            if ((keys[mid] >> ebits) < q) l = mid + 1;
+            else h = mid;
+        }
+        const uint64_t v = uscan[l];
+        out_off[q] = v;
+        if (q == nq && out_total) *out_total = v;
+    }
+}
+
+template <bool U32>
+__global__ void k_ed_scatter(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ vals,
+                             const uint64_t* __restrict__ uscan, uint64_t P, uint32_t ebits,
+                             void* __restrict__ out_end, uint8_t* __restrict__ out_dist, uint64_t capacity) {
+    GRID_STRIDE(p, P) {
+        const uint64_t key = keys[p];
+        if (p && keys[p - 1] == key) continue;
+        const uint64_t o = uscan[p];
+        if (o >= capacity) continue;
+        const uint64_t e = key & ((1ull << ebits) - 1ull);
+        if (U32) static_cast<uint32_t*>(out_end)[o] = (uint32_t)e;
+        else static_cast<uint64_t*>(out_end)[o] = e;
+        if (out_dist) out_dist[o] = vals[p];
+    }
+}
+
+// SAS_ED_TIMING=1: the verify kernel and the de-duplication (k_ed_emit .. k_ed_offsets) of every
+// call are timed with HIP events (synchronises); sas_locate_edit_verify_ms and
+// sas_locate_edit_dedup_ms return the calling thread's last figures
+static thread_local double ed_last_verify_ms = -1.0;
+static thread_local double ed_last_dedup_ms = -1.0;  // k_ed_emit .. k_ed_offsets
+static thread_local uint64_t ed_last_candidates = 0, ed_last_proposals = 0;
+static bool ed_timing() {
+    const char* e = getenv("SAS_ED_TIMING");
+    return e && e[0] == '1';
+}
+
+extern "C" double sas_locate_edit_verify_ms(uint64_t* candidates) {
+    if (candidates) *candidates = ed_last_candidates;
+    return ed_last_verify_ms;
+}
+
+extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
+    if (proposals) *proposals = ed_last_proposals;
+    return ed_last_dedup_ms;
+}
+
+static uint32_t ed_bits(uint64_t v) {  // bits that hold every value in [0, v]
+    uint32_t b = 1;
+    while (b < 64 && (v >> b)) b++;
+    return b;
+}
+
+struct EdEvent {  // destroyed on every way out
+    hipEvent_t e = nullptr;
+    ~EdEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
+// Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
+struct EdState {
+    hipMemPool_t pool = nullptr;
+    MmPoolBuf poff, plen, lohi, coff, qfl, mask, kbase, dists, pscan, keys, vals, uscan;
+    const uint64_t* skeys = nullptr;  // the sorted proposals
+    const uint8_t* svals = nullptr;
+    uint64_t C = 0, P = 0;
+    uint32_t ebits = 0;
+};
+
+template <int NW>
+static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, const EdArgs& a) {
+    if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW>), grid, dim3(MM_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_ed_verify<4, NW>), grid, dim3(MM_BLOCK), 0, st, a);
+}
+
+// All arrays on the device (out_total may be null).  Two host reads: the candidate total and
+// the proposal total
+static int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off,
+                      uint8_t* out_qflags, uint64_t* out_total, hipStream_t st, uint32_t flags, EdState& s) {
+    const uint32_t kp1 = k + 1;
+    const uint64_t nq = Q.nq, np = nq * kp1;
+    s.ebits = ed_bits(x->n);
+    TRY(sas_scratch_pool(x, &s.pool));
+    TRY(s.poff.alloc(s.pool, np * 8, st));
+    TRY(s.plen.alloc(s.pool, np * 4, st));
+    TRY(s.lohi.alloc(s.pool, np * 16, st));
+    TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
+    if (!out_qflags) {
+        TRY(s.qfl.alloc(s.pool, nq, st));
+        out_qflags = s.qfl.as<uint8_t>();
+    }
+    uint64_t* lo = s.lohi.as<uint64_t>();
+    uint64_t* hi = lo + np;
+    const unsigned cap_grid = (unsigned)x->num_cus * 8;
+    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto nothing = [&]() {
+        HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
+        if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
+        return 0;
+    };
+    hipLaunchKernelGGL(k_mm_pieces, grid(np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(), s.plen.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
+    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, lo, hi, st, rflags));
+    hipLaunchKernelGGL(k_ed_gate, grid(nq), dim3(256), 0, st, Q, kp1, max_seed_hits, lo, hi, out_qflags);
+    HIP_TRY(hipGetLastError());
+    TRY(sas_locate_offsets(x, lo, hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS));
+    HIP_TRY(hipMemcpyAsync(&s.C, s.coff.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t C = s.C;
+    ed_last_candidates = C;
+    ed_last_verify_ms = ed_last_dedup_ms = -1.0;
+    ed_last_proposals = 0;
+    if (C == 0) return nothing();
+    TRY(s.mask.alloc(s.pool, (C + 1) * 4, st));
+    TRY(s.kbase.alloc(s.pool, C * 8, st));
+    TRY(s.dists.alloc(s.pool, C * 16, st));
+    TRY(s.pscan.alloc(s.pool, (C + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(s.mask.as<uint32_t>() + C, 0, 4, st));
+    EdArgs a{};
+    a.tw = x->text_w;
+    a.n = x->n;
+    a.sa = x->sa;
+    a.Q = Q;
+    a.k = k;
+    a.ebits = s.ebits;
+    a.lo = lo;
+    a.coff = s.coff.as<uint64_t>();
+    a.np = np;
+    a.C = C;
+    a.mask = s.mask.as<uint32_t>();
+    a.kbase = s.kbase.as<uint64_t>();
+    a.dists = s.dists.as<ulonglong2>();
+    uint64_t blocks = (C + MM_T - 1) / MM_T;
+    if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
+    const dim3 vgrid((unsigned)blocks);
+    EdEvent ev0, ev1;
+    const bool timing = ed_timing();
+    if (timing) {
+        HIP_TRY(hipEventCreate(&ev0.e));
+        HIP_TRY(hipEventCreate(&ev1.e));
+        HIP_TRY(hipEventRecord(ev0.e, st));
+    }
+    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
+    // fixed-length batches: the word count from m (a longer m is gated: any kernel serves)
+    if (Q.qoff) ed_launch_verify<0>(x, vgrid, st, a);
+    else if (Q.m <= 64) ed_launch_verify<1>(x, vgrid, st, a);
+    else if (Q.m <= 128) ed_launch_verify<2>(x, vgrid, st, a);
+    else ed_launch_verify<4>(x, vgrid, st, a);
+    HIP_TRY(hipGetLastError());
+    if (timing) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        ed_last_verify_ms = ms;
+    }
+    // proposals: one per accepted end of every candidate
+    TRY(mm_scan(s.pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
+                s.pscan.as<uint64_t>(), C + 1));
+    HIP_TRY(hipMemcpyAsync(&s.P, s.pscan.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t P = s.P;
+    ed_last_proposals = P;
+    if (P == 0) return nothing();
+    if (timing) HIP_TRY(hipEventRecord(e0, st));
+    TRY(s.keys.alloc(s.pool, 2 * P * 8, st));
+    TRY(s.vals.alloc(s.pool, 2 * P, st));
+    TRY(s.uscan.alloc(s.pool, (P + 1) * 8, st));
+    uint64_t* keys = s.keys.as<uint64_t>();
+    uint8_t* vals = s.vals.as<uint8_t>();
+    hipLaunchKernelGGL(k_ed_emit, grid(C), dim3(256), 0, st, s.mask.as<uint32_t>(), s.kbase.as<uint64_t>(),
+                       s.dists.as<ulonglong2>(), s.pscan.as<uint64_t>(), C, keys, vals);
+    HIP_TRY(hipGetLastError());
+    const uint32_t kbits = std::min<uint32_t>(64, s.ebits + (nq > 1 ? ed_bits(nq - 1) : 0));
+    rocprim::double_buffer<uint64_t> kdb(keys, keys + P);
+    rocprim::double_buffer<uint8_t> vdb(vals, vals + P);
+    {
+        size_t tbytes = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
+        MmPoolBuf tmp;
+        TRY(tmp.alloc(s.pool, tbytes, st));
+        HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
+    }
+    s.skeys = kdb.current();
+    s.svals = vdb.current();
+    TRY(mm_scan(s.pool, st,
+                rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), EdFirst{s.skeys, P}),
+                s.uscan.as<uint64_t>(), P + 1));
+    hipLaunchKernelGGL(k_ed_offsets, grid(nq + 1), dim3(256), 0, st, s.skeys, s.uscan.as<uint64_t>(), P, nq, s.ebits,
+                       out_off, out_total);
+    HIP_TRY(hipGetLastError());
+    if (timing) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        ed_last_dedup_ms = ms;
+    }
+    return 0;
+}
+
+static int ed_scatter(const sas_index* x, EdState& s, void* out_end, uint8_t* out_dist, uint64_t capacity,
+                      hipStream_t st, uint32_t flags) {
+    if (s.P == 0 || capacity == 0) return 0;
+    const dim3 grid(std::min(grid_for(s.P), (unsigned)x->num_cus * 8));
+    if (flags & SAS_LOCATE_U32)
+        hipLaunchKernelGGL(k_ed_scatter<true>, grid, dim3(256), 0, st, s.skeys, s.svals, s.uscan.as<uint64_t>(), s.P,
+                           s.ebits, out_end, out_dist, capacity);
+    else
+        hipLaunchKernelGGL(k_ed_scatter<false>, grid, dim3(256), 0, st, s.skeys, s.svals, s.uscan.as<uint64_t>(), s.P,
+                           s.ebits, out_end, out_dist, capacity);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int edit_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
+                     const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
+                     uint64_t* out_off, void* out_end, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
+                     uint64_t* out_total, void* stream, uint32_t flags) {
+    const std::string w(fn);
+    if (!x) SAS_FAIL(EINVAL, w + ": null index");
+    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
+    if (x->tag_lines || x->sa_w == 8)
+        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
+    if (x->rank_lo != 0 || x->sa_n != x->n)
+        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
+    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
+    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
+    if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_end) ||
+        (!dev && !out_total))
+        SAS_FAIL(EINVAL, w + ": null argument");
+    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
+        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
+    // the (query, end) sort key: the bits of an end in [0, n] above those of a query number
+    if (ed_bits(x->n) + (nq > 1 ? ed_bits(nq - 1) : 0) > 64)
+        SAS_FAIL(EINVAL, w + ": " + std::to_string(nq) + " queries on a text of " + std::to_string(x->n) +
+                             " chars do not fit the 64-bit (query, end) sort key: split the batch");
+    // the range search's own requirements (its error is passed on)
+    TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
+    HIP_TRY(hipSetDevice(x->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (nq == 0) {
+        if (dev) {
+            HIP_TRY(hipMemsetAsync(out_off, 0, 8, st));
+            if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
+        } else {
+            out_off[0] = 0;
+            *out_total = 0;
+        }
+        return 0;
+    }
+    EdState s;
+    if (dev) {
+        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
+        TRY(ed_prepare(x, Q, k, max_seed_hits, out_off, out_qflags, out_total, st, flags, s));
+        return ed_scatter(x, s, out_end, out_dist, capacity, st, flags);
+    }
+    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
+    uint64_t span = nq * (uint64_t)m;
+    if (ragged) {
+        span = 0;
+        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
+    }
+    DevBuf dq, dqoff, dqlen, doff, dfl, dend, ddist;
+    TRY(dq.alloc(span + 64, "edit queries"));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
+    if (ragged) {
+        TRY(dqoff.alloc(nq * 8, "edit offsets"));
+        TRY(dqlen.alloc(nq * 4, "edit lengths"));
+        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
+    }
+    TRY(doff.alloc((nq + 1) * 8, "edit result offsets"));
+    TRY(dfl.alloc(nq, "edit query flags"));
+    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
+    TRY(ed_prepare(x, Q, k, max_seed_hits, doff.as<uint64_t>(), dfl.as<uint8_t>(), nullptr, st, flags | SAS_VALIDATE,
+                   s));
+    HIP_TRY(hipMemcpyAsync(out_off, doff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (out_qflags) HIP_TRY(hipMemcpyAsync(out_qflags, dfl.p, nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t total = out_off[nq];
+    *out_total = total;
+    if (total > capacity)
+        SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " ends, capacity " + std::to_string(capacity) +
+                             " (size out_end from *out_total and call again)");
+    if (total == 0) return 0;
+    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8;
+    TRY(dend.alloc(total * esz, "edit ends"));
+    if (out_dist) TRY(ddist.alloc(total, "edit distances"));
+    TRY(ed_scatter(x, s, dend.p, out_dist ? ddist.as<uint8_t>() : nullptr, total, st, flags));
+    HIP_TRY(hipMemcpyAsync(out_end, dend.p, total * esz, hipMemcpyDeviceToHost, st));
+    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, ddist.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int sas_locate_edit(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                               uint64_t nq, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off, void* out_end,
+                               uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
+                               void* stream, uint32_t flags) {
+    return edit_impl("sas_locate_edit", x, qbytes, true, qoff, qlen, 0, nq, k, max_seed_hits, out_off, out_end,
+                     out_dist, out_qflags, capacity, out_total, stream, flags);
+}
+
+extern "C" int sas_locate_edit_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                                     uint64_t max_seed_hits, uint64_t* out_off, void* out_end, uint8_t* out_dist,
+                                     uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
+                                     uint32_t flags) {
+    return edit_impl("sas_locate_edit_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, max_seed_hits, out_off,
+                     out_end, out_dist, out_qflags, capacity, out_total, stream, flags);
+}

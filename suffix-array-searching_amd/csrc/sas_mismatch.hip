@@ -37,9 +37,8 @@
 // (k_mm_prepack) and reads one 8-B word per step: the verify kernel is then faster on long
 // queries, the whole call slower on every shape measured (the A/B of tools/bench_mismatch.py;
 // DESIGN.md has both figures).
-#include "build_util.hpp"
+#include "seed_verify.hpp"
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
@@ -47,38 +46,7 @@
 #include <cstring>
 #include <vector>
 
-#define MM_BLOCK 256
-#define MM_T 2048          // candidates per tile
-#define MM_PER (MM_T / MM_BLOCK)
-#define MM_SLICE 4096      // candidate offsets of a tile staged in LDS (16 KiB)
-#define MM_MAX_GRID (1u << 20)
-#define MM_MAX_K 15
 #define MM_REJECT 0xFFu
-
-struct MmQueries {
-    const uint8_t* qbytes;
-    const uint64_t* qoff;  // null: fixed-length queries of m chars
-    const uint32_t* qlen;
-    uint32_t m;
-    uint64_t nq;
-    __device__ __forceinline__ uint64_t off(uint64_t q) const { return qoff ? qoff[q] : q * (uint64_t)m; }
-    __device__ __forceinline__ uint32_t len(uint64_t q) const { return qoff ? qlen[q] : m; }
-};
-
-// b_j: the first char of piece j of a query of m chars cut into kp1 pieces
-__device__ __forceinline__ uint32_t mm_piece_start(uint32_t j, uint32_t m, uint32_t kp1) {
-    return (uint32_t)(((uint64_t)j * m) / kp1);
-}
-
-__global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff, uint32_t* __restrict__ plen) {
-    GRID_STRIDE(i, Q.nq * kp1) {
-        const uint64_t q = i / kp1;
-        const uint32_t j = (uint32_t)(i - q * kp1), m = Q.len(q);
-        const uint32_t b0 = mm_piece_start(j, m, kp1), b1 = mm_piece_start(j + 1, m, kp1);
-        poff[i] = Q.off(q) + b0;
-        plen[i] = b1 - b0;
-    }
-}
 
 // One thread per query: skipped seeds and short queries lose their ranges
 __global__ void k_mm_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint64_t* __restrict__ lo,
@@ -115,17 +83,6 @@ __global__ void k_mm_prepack(MmQueries Q, const uint64_t* __restrict__ woff, uin
         uint64_t* w = qw + woff[q];
         for (uint32_t j = 0; j < nw; j++) w[j] = pack_query_word(b, m, j, &bad);
     }
-}
-
-// the last i in [0, np] with off[i] <= v (off[0] = 0): for v below the total a non-empty piece
-__device__ __forceinline__ uint64_t mm_piece_of(const uint64_t* __restrict__ off, uint64_t np, uint64_t v) {
-    uint64_t l = 0, h = np + 1;
-    while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if (off[mid] <= v) l = mid + 1;
-        else h = mid;
-    }
-    return l ? l - 1 : 0;
 }
 
 struct MmArgs {
@@ -194,55 +151,9 @@ __global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
         const uint64_t t0 = tile * (uint64_t)MM_T;
         const uint64_t t1 = t0 + MM_T < C ? t0 + MM_T : C;
         const uint32_t n_el = (uint32_t)(t1 - t0);
-        // the pieces of the tile's first and last candidate (both non-empty)
-        if (tid < 2) sh_p[tid] = mm_piece_of(a.coff, a.np, tid ? t1 - 1 : t0);
-        __syncthreads();
-        const uint64_t p0 = sh_p[0];
-        uint64_t p1 = sh_p[1];
-        if (p1 < p0) p1 = p0;
-        if (p1 > a.np - 1) p1 = a.np - 1;
-        const uint64_t nps = p1 - p0 + 1;
-        const uint32_t staged = nps <= MM_SLICE ? 1u : 0u;
-        if (staged) {
-            for (uint32_t x = tid; x < (uint32_t)nps; x += MM_BLOCK) {
-                const uint64_t o = a.coff[p0 + x];
-                rel[x] = o <= t0 ? 0u : (o - t0 >= MM_T ? (uint32_t)MM_T : (uint32_t)(o - t0));
-            }
-            __syncthreads();
-        }
-        // element e of the tile belongs to the last piece x in [p0, p1] with coff[x] <= t0 + e
-        uint64_t pi[MM_PER], rk[MM_PER];
+        uint64_t pi[MM_PER], pv[MM_PER];
         uint32_t ok[MM_PER];
-#pragma unroll
-        for (int u = 0; u < MM_PER; u++) {
-            const uint32_t e = u * MM_BLOCK + tid;
-            const uint64_t c = t0 + e;
-            ok[u] = e < n_el ? 1u : 0u;
-            pi[u] = rk[u] = 0;
-            if (ok[u]) {
-                uint64_t l = 1, h = nps;
-                if (staged) {
-                    while (l < h) {
-                        const uint64_t mid = (l + h) >> 1;
-                        if (rel[mid] <= e) l = mid + 1;
-                        else h = mid;
-                    }
-                } else {
-                    while (l < h) {
-                        const uint64_t mid = (l + h) >> 1;
-                        if (a.coff[p0 + mid] <= c) l = mid + 1;
-                        else h = mid;
-                    }
-                }
-                pi[u] = p0 + l - 1;
-                const uint64_t o = a.coff[pi[u]];
-                rk[u] = a.lo[pi[u]] + (c - o);
-                ok[u] = (o <= c && c < a.coff[pi[u] + 1] && rk[u] < a.n) ? 1u : 0u;
-            }
-        }
-        uint64_t pv[MM_PER];  // all of a thread's SA reads are issued before the first is used
-#pragma unroll
-        for (int u = 0; u < MM_PER; u++) pv[u] = ok[u] ? sa[rk[u]] : 0;
+        mm_tile_candidates(sa, a.coff, a.lo, a.np, a.n, t0, n_el, rel, sh_p, pi, pv, ok);
 #pragma unroll
         for (int u = 0; u < MM_PER; u++) {
             const uint32_t e = u * MM_BLOCK + tid;
@@ -284,39 +195,6 @@ __global__ void k_mm_scatter(const uint8_t* __restrict__ verdict, const uint64_t
         else static_cast<uint64_t*>(out_pos)[o] = cpos[c];
         if (out_dist) out_dist[o] = (uint8_t)v;
     }
-}
-
-struct MmPoolBuf {  // stream-ordered scratch from the index's pool
-    void* p = nullptr;
-    hipStream_t st = nullptr;
-    ~MmPoolBuf() { if (p) (void)hipFreeAsync(p, st); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-    int alloc(hipMemPool_t pool, size_t bytes, hipStream_t s) {
-        st = s;
-        HIP_TRY(hipMallocFromPoolAsync(&p, bytes ? bytes : 8, pool, s));
-        return 0;
-    }
-};
-
-static int mm_scan(hipMemPool_t pool, hipStream_t st, const uint8_t* verdict, uint64_t* scan, uint64_t count) {
-    auto in = rocprim::make_transform_iterator(verdict, MmAccept{});
-    size_t tbytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, in, scan, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
-                                    st));
-    MmPoolBuf tmp;
-    TRY(tmp.alloc(pool, tbytes, st));
-    HIP_TRY(rocprim::exclusive_scan(tmp.p, tbytes, in, scan, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
-                                    st));
-    return 0;
-}
-
-static int mm_scan_u64(hipMemPool_t pool, hipStream_t st, uint64_t* v, uint64_t count) {
-    size_t tbytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, v, v, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(), st));
-    MmPoolBuf tmp;
-    TRY(tmp.alloc(pool, tbytes, st));
-    HIP_TRY(rocprim::exclusive_scan(tmp.p, tbytes, v, v, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(), st));
-    return 0;
 }
 
 // SAS_MM_QWORDS=packed: pack every query once into scratch (the A/B knob; read at every call,
@@ -382,7 +260,7 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         TRY(s.woff.alloc(s.pool, (nq + 1) * 8, st));
         hipLaunchKernelGGL(k_mm_wcount, grid(nq + 1), dim3(256), 0, st, Q, s.woff.as<uint64_t>());
         HIP_TRY(hipGetLastError());
-        TRY(mm_scan_u64(s.pool, st, s.woff.as<uint64_t>(), nq + 1));
+        TRY(mm_scan(s.pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
         if (Q.qoff) HIP_TRY(hipMemcpyAsync(&words, s.woff.as<uint64_t>() + nq, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipMemcpyAsync(&s.C, s.coff.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, st));
@@ -446,7 +324,8 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         (void)hipEventDestroy(e1);
         mm_last_verify_ms = ms;
     }
-    TRY(mm_scan(s.pool, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(), C + 1));
+    TRY(mm_scan(s.pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
+                s.scan.as<uint64_t>(), C + 1));
     hipLaunchKernelGGL(k_mm_offsets, grid(nq + 1), dim3(256), 0, st, s.coff.as<uint64_t>(), s.scan.as<uint64_t>(), nq,
                        kp1, out_off, out_total);
     HIP_TRY(hipGetLastError());

@@ -31,6 +31,9 @@ SAS_LOCATE_NO_PARTITION = 1 << 30
 SAS_ROUTE_PACKED = 1 << 26
 SAS_MM_TRUNCATED = 1  # sas_locate_mismatch's per-query flags
 SAS_MM_SHORT = 2
+SAS_ED_TRUNCATED = 1  # sas_locate_edit's per-query flags
+SAS_ED_SHORT = 2
+SAS_ED_LONG = 4
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
 SAS_BUILD_SA40 = 1 << 8
@@ -175,6 +178,12 @@ def lib():
     L.sas_locate_mismatch_fixed.argtypes = [vp, vp, u32, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
     L.sas_locate_mismatch_verify_ms.argtypes = [vp]
     L.sas_locate_mismatch_verify_ms.restype = C.c_double
+    L.sas_locate_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
+    L.sas_locate_edit_fixed.argtypes = [vp, vp, u32, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
+    L.sas_locate_edit_verify_ms.argtypes = [vp]
+    L.sas_locate_edit_verify_ms.restype = C.c_double
+    L.sas_locate_edit_dedup_ms.argtypes = [vp]
+    L.sas_locate_edit_dedup_ms.restype = C.c_double
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

@@ -709,15 +709,17 @@ class SaNaive:
         plen = int(pattern.numel() if _is_cuda(pattern) else len(pattern))
         return self._match("stats", pattern, None, None, int(max_len), plen, ranges, stream, flags)
 
-    # -- k-mismatch locate (sas_locate_mismatch*)
-    def _locate_mismatch(self, qbytes, qoff, qlen, m, nq, k, max_seed_hits, u32, dist, stream, out, capacity, flags):
+    # -- k-mismatch and k-difference locate (sas_locate_mismatch*, sas_locate_edit*: one contract)
+    def _locate_mismatch(self, qbytes, qoff, qlen, m, nq, k, max_seed_hits, u32, dist, stream, out, capacity, flags,
+                         fn="sas_locate_mismatch"):
         L = lib()
+        ragged_fn, fixed_fn = getattr(L, fn), getattr(L, fn + "_fixed")
 
         def call(off, pos, dst, qfl, cap, total, st, fl):
             tail = (int(k), int(max_seed_hits), _ptr(off), _ptr(pos), _ptr(dst), _ptr(qfl), int(cap), total, st, fl)
             if qoff is not None:
-                return L.sas_locate_mismatch(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *tail)
-            return L.sas_locate_mismatch_fixed(self._h, _ptr(qbytes), m, nq, *tail)
+                return ragged_fn(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *tail)
+            return fixed_fn(self._h, _ptr(qbytes), m, nq, *tail)
 
         if _is_cuda(qbytes):
             import torch
@@ -734,10 +736,10 @@ class SaNaive:
             if out is None:
                 out = torch.empty(max(int(capacity), 1), dtype=dt, device=d)
             elif not _is_cuda(out) or out.dtype != dt or not out.is_contiguous():
-                raise ValueError(f"locate_mismatch: out must be a contiguous CUDA {dt} tensor")
+                raise ValueError(f"{fn[4:]}: out must be a contiguous CUDA {dt} tensor")
             capacity = out.numel() if capacity is None else capacity
             if capacity > out.numel():
-                raise ValueError("locate_mismatch: capacity exceeds out")
+                raise ValueError(f"{fn[4:]}: capacity exceeds out")
             dst = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=d) if dist else None
             if total != 0:
                 check(call(off, out, dst, qfl, capacity, None, st, fl))
@@ -784,6 +786,36 @@ class SaNaive:
         nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
         return self._locate_mismatch(qbytes, None, None, int(m), nq, k, max_seed_hits, u32, dist, stream, out,
                                      capacity, flags)
+
+    def locate_edit(self, qbytes, qoff, qlen, k: int, max_seed_hits: int = 0, u32: bool = False,
+                    dist: bool = True, stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """Every end position of every ragged query qbytes[qoff[i] : qoff[i] + qlen[i]] within edit
+        distance k (sas_locate_edit, Sellers' problem): (off, end, dist, qflags).  With D(e) = the
+        least unit-cost edit distance between query i and a text substring that ends at e, query
+        i's ends are end[off[i] : off[i + 1]], every e in [0, n] with D(e) <= k in ascending order;
+        dist holds D(e) (None with dist=False).  The neighbouring ends of one alignment are all
+        reported; where an alignment starts is not.  qflags[i] is a mask of SAS_ED_TRUNCATED (a
+        seed occurred more than max_seed_hits times and was skipped; 0: no limit), SAS_ED_SHORT
+        (len <= k: no result) and SAS_ED_LONG (len > 256: no result).  numpy in -> numpy out (a
+        sizing call, then the real one); torch CUDA in -> CUDA out: with out / capacity one call
+        that writes nothing at or past the capacity (the caller checks off[nq]), otherwise a
+        sizing call first."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._locate_mismatch(qbytes, qoff, qlen, 0, nq, k, max_seed_hits, u32, dist, stream, out, capacity,
+                                     flags, fn="sas_locate_edit")
+
+    def locate_edit_fixed(self, qbytes, m: int, k: int, max_seed_hits: int = 0, u32: bool = False,
+                          dist: bool = True, stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """locate_edit for fixed-length queries qbytes[i*m : (i+1)*m] (sas_locate_edit_fixed)."""
+        if m <= 0:
+            raise ValueError("use locate_edit for empty queries")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._locate_mismatch(qbytes, None, None, int(m), nq, k, max_seed_hits, u32, dist, stream, out,
+                                     capacity, flags, fn="sas_locate_edit")
 
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
