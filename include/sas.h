@@ -623,6 +623,59 @@ int sas_locate_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_
 double sas_locate_edit_verify_ms(uint64_t* candidates);
 double sas_locate_edit_dedup_ms(uint64_t* proposals);
 
+/* Where an approximate match starts and its edit script, for ends that sas_locate_edit*
+ * reported (or any other ends).  For a query q of m chars, an end e in [0, n] and a bound k in
+ * 0..15 (EINVAL above):
+ *   - w0 = max(0, e - m - k);
+ *   - for 0 <= i <= m and w0 <= j <= e, R[i][j] = ed(q[i .. m), t[j .. e)), the unit-cost edit
+ *     distance of the query suffix and the text slice;
+ *   - d = min over j of R[0][j].  Whenever D(e) <= k this is D(e) itself: an alignment of cost
+ *     <= k that ends at e cannot start before e - m - k.
+ * Reported per alignment:
+ *   - start: s = the largest j with R[0][j] = d, the shortest text substring that reaches the
+ *     distance;
+ *   - script: walk forward from (i, j) = (0, s) until (m, e); at each cell the first rule that
+ *     applies:
+ *       1. i < m, j < e and R[i+1][j+1] + (q[i] != t[j]) == R[i][j]: emit SAS_AL_EQ if the chars
+ *          are equal, else SAS_AL_X; both advance;
+ *       2. j < e and R[i][j+1] + 1 == R[i][j]: emit SAS_AL_DEL (a text char that the query
+ *          lacks); j advances;
+ *       3. otherwise emit SAS_AL_INS (a query char that the text lacks); i advances.
+ *     The script is run-length encoded as runs of equal ops, each (len << 2) | op in a uint16_t;
+ *     it has at most 2k + 1 runs, because at most k ops are not SAS_AL_EQ;
+ *   - no alignment: start = n, dist = SAS_AL_NONE_DIST, nruns = 0 and all run slots 0, when
+ *     m == 0, m > SAS_ED_MAX_M, e > n or d > k.
+ * The rule is deterministic and independent of how it is computed.  Nothing outside t[w0 .. e)
+ * takes part: neither a char before w0 nor the zero padding behind the text.
+ * off[0..nq] (u64) and end[] (u64, or u32 with SAS_LOCATE_U32) are what sas_locate_edit* wrote:
+ * alignment a belongs to the query i with off[i] <= a < off[i+1].  out_start (u64, or u32 with
+ * SAS_LOCATE_U32, which needs n < 2^32: EINVAL otherwise), out_dist, out_nruns (one byte each)
+ * and out_runs[a * (2k + 1) + r] are written for every a < min(na, off[nq]); run slots that are
+ * not used are written as 0; nothing at or past that bound is touched.  out_dist, out_nruns and
+ * out_runs may each be NULL.  EINVAL for a null index and, when na > 0, for a null off, end or
+ * out_start.  Flags: SAS_DEVICE_PTRS, SAS_LOCATE_U32, SAS_VALIDATE.
+ * The call reads only the packed text, never the SA: every index is served, shards and parts
+ * (their text is whole) and SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES indexes (they keep the text)
+ * included.
+ * With SAS_DEVICE_PTRS the call is asynchronous on `stream` and synchronises nowhere (the grid
+ * and the scratch, from the index's stream-ordered pool, are sized from na), so it chains behind
+ * sas_locate_edit on the same stream; SAS_VALIDATE rejects query bytes > 3 and synchronises to
+ * do so.  With host pointers: synchronous, bytes always validated. */
+#define SAS_AL_EQ  0u /* run ops: (len << 2) | op in a uint16_t; len <= m + k < 2^14 */
+#define SAS_AL_X   1u
+#define SAS_AL_INS 2u /* query char absent from the text */
+#define SAS_AL_DEL 3u /* text char absent from the query */
+#define SAS_AL_NONE_DIST 255u
+int sas_align_edit(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                   uint64_t nq, uint32_t k, const uint64_t* off, const void* end, uint64_t na,
+                   void* out_start, uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs,
+                   void* stream, uint32_t flags);
+/* sas_align_edit for fixed-length queries qbytes[k*m .. (k+1)*m). */
+int sas_align_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                         const uint64_t* off, const void* end, uint64_t na, void* out_start,
+                         uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs, void* stream,
+                         uint32_t flags);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

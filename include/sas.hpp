@@ -340,6 +340,43 @@ class SaNaive {
         return r;
     }
 
+    /* Result of align_edit, one entry per end of an Edited: start[a] is the largest s with
+     * ed(query, t[s .. end[a])) = dist[a], the least distance of any start; the script from
+     * (0, s) is runs[a * stride .. a * stride + nruns[a]), each run (len << 2) | op with op one of
+     * SAS_AL_EQ, SAS_AL_X, SAS_AL_INS and SAS_AL_DEL; stride = 2k + 1, unused slots are 0.  An end
+     * without an alignment within k has start = n, dist = SAS_AL_NONE_DIST and nruns = 0 */
+    struct Aligned {
+        std::vector<uint64_t> start;
+        std::vector<uint8_t> dist, nruns;
+        std::vector<uint16_t> runs;
+        size_t stride = 1;
+    };
+
+    /* where the alignment of every end of `e` (locate_edit of the same queries) starts, and its
+     * edit script, in one call (sas_align_edit: a banded pass and a walk per end on the GPU) */
+    Aligned align_edit(const std::vector<Seq>& qs, uint32_t k, const Edited& e, uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Aligned r;
+        const size_t na = e.end.size();
+        r.stride = 2 * (size_t)k + 1;
+        r.start.assign(na, n_);
+        r.dist.assign(na, (uint8_t)SAS_AL_NONE_DIST);
+        r.nruns.assign(na, 0);
+        r.runs.assign(na * r.stride, 0);
+        if (na)
+            check(sas_align_edit(h_, bytes.data(), qoff.data(), len.data(), qs.size(), k, e.off.data(), e.end.data(),
+                                 na, r.start.data(), r.dist.data(), r.nruns.data(), r.runs.data(), nullptr, flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are
@@ -412,6 +449,18 @@ inline double bench_batch(const SaNaive& sa, const std::vector<Seq>& queries, co
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "%-20s: %8.2fs %6.0fns %6.0fns %5.2f\n", name, s, s * 1e9 / queries.size(),
                  s * 1e9 / (cnt ? cnt : 1), (double)cnt / queries.size());
+    return s;
+}
+
+/* the script of alignment a of an Aligned as a string such as "17=1X14=": = a match, X a
+ * substitution, I a query char that the text lacks, D a text char that the query lacks */
+inline std::string cigar(const SaNaive::Aligned& r, size_t a) {
+    std::string s;
+    for (size_t i = 0; i < r.nruns[a]; i++) {
+        const uint16_t run = r.runs[a * r.stride + i];
+        s += std::to_string(run >> 2);
+        s += "=XID"[run & 3u];
+    }
     return s;
 }
 

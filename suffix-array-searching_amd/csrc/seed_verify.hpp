@@ -29,7 +29,7 @@ __device__ __forceinline__ uint32_t mm_piece_start(uint32_t j, uint32_t m, uint3
     return (uint32_t)(((uint64_t)j * m) / kp1);
 }
 
-static __global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff,
+[[maybe_unused]] static __global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff,
                                    uint32_t* __restrict__ plen) {
     GRID_STRIDE(i, Q.nq * kp1) {
         const uint64_t q = i / kp1;

@@ -817,12 +817,86 @@ class SaNaive:
         return self._locate_mismatch(qbytes, None, None, int(m), nq, k, max_seed_hits, u32, dist, stream, out,
                                      capacity, flags, fn="sas_locate_edit")
 
+    # -- alignment start and edit script of each reported end (sas_align_edit*)
+    def _align_edit(self, qbytes, qoff, qlen, m, nq, k, off, end, u32, stream, flags):
+        L = lib()
+        k = int(k)
+        stride = 2 * k + 1
+
+        def call(na, start, dist, nruns, runs, st, fl):
+            tail = (k, _ptr(off), _ptr(end), int(na), _ptr(start), _ptr(dist), _ptr(nruns), _ptr(runs), st, fl)
+            if qoff is not None:
+                return L.sas_align_edit(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *tail)
+            return L.sas_align_edit_fixed(self._h, _ptr(qbytes), m, nq, *tail)
+
+        if _is_cuda(qbytes):
+            import torch
+            d = qbytes.device
+            dt = torch.int32 if u32 else torch.int64
+            if not (_is_cuda(off) and _is_cuda(end)) or off.dtype != torch.int64 or end.dtype != dt:
+                raise ValueError(f"align_edit: off must be a CUDA int64 tensor and end a CUDA {dt} tensor")
+            off, end = off.contiguous(), end.contiguous()
+            na = int(end.numel())
+            st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+            fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+            # an alignment past off[nq] is not written: it reads as "none"
+            start = torch.full((na,), self.n, dtype=dt, device=d)
+            dist = torch.full((na,), _lib.SAS_AL_NONE_DIST, dtype=torch.uint8, device=d)
+            nruns = torch.zeros(na, dtype=torch.uint8, device=d)
+            runs = torch.zeros((na, stride), dtype=torch.int16, device=d)
+            check(call(na, start, dist, nruns, runs, st, fl))
+            return start, dist, nruns, runs
+        qbytes = _as_u8(qbytes)
+        off = np.ascontiguousarray(off, np.uint64)
+        end = np.ascontiguousarray(end, np.uint32 if u32 else np.uint64)
+        na = len(end)
+        fl = flags | (_lib.SAS_LOCATE_U32 if u32 else 0)
+        start = np.full(na, self.n, np.uint32 if u32 else np.uint64)
+        dist = np.full(na, _lib.SAS_AL_NONE_DIST, np.uint8)
+        nruns = np.zeros(na, np.uint8)
+        runs = np.zeros((na, stride), np.uint16)
+        check(call(na, start, dist, nruns, runs, stream, fl))
+        return start, dist, nruns, runs
+
+    def align_edit(self, qbytes, qoff, qlen, k: int, off, end, u32: bool = False, flags: int = 0, stream=None):
+        """Where each reported end's alignment starts, and its edit script (sas_align_edit):
+        (start, dist, nruns, runs) for the ends end[off[i] : off[i + 1]] of the ragged queries
+        qbytes[qoff[i] : qoff[i] + qlen[i]], as locate_edit returned them (u32: end and start hold
+        32-bit positions).  start[a] is the largest s with ed(query, t[s : end[a]]) = dist[a], the
+        least distance of any start; runs[a, :nruns[a]] is the run-length encoded script from
+        (0, s), each run (len << 2) | op with op one of SAS_AL_EQ, SAS_AL_X, SAS_AL_INS (a query
+        char that the text lacks) and SAS_AL_DEL (a text char that the query lacks); runs has
+        2k + 1 columns, the unused ones 0 (sas_amd.cigar prints a row).  An end without an
+        alignment within k has start = n, dist = 255 and nruns = 0.  numpy in -> numpy out; torch
+        CUDA in -> CUDA out (runs as int16), asynchronous on the stream, no host read."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._align_edit(qbytes, qoff, qlen, 0, nq, k, off, end, u32, stream, flags)
+
+    def align_edit_fixed(self, qbytes, m: int, k: int, off, end, u32: bool = False, flags: int = 0, stream=None):
+        """align_edit for fixed-length queries qbytes[i*m : (i+1)*m] (sas_align_edit_fixed)."""
+        if m <= 0:
+            raise ValueError("use align_edit for empty queries")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._align_edit(qbytes, None, None, int(m), nq, k, off, end, u32, stream, flags)
+
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
         kn, cn = C.c_double(0), C.c_double(0)
         check(lib().sas_time_fixed(self._h, _ptr(d_qbytes), m, nq, _lib.ALGOS[algo], _ptr(d_out), reps, stream,
                                    flags, C.byref(kn), C.byref(cn)))
         return kn.value, cn.value
+
+
+def cigar(runs_row, nruns) -> str:
+    """The script of one alignment of SaNaive.align_edit as a string such as "17=1X14=": the first
+    `nruns` runs of the row, = a match, X a substitution, I a query char that the text lacks, D
+    a text char that the query lacks."""
+    row = runs_row.cpu().numpy() if hasattr(runs_row, "cpu") else np.asarray(runs_row)
+    return "".join(f"{int(r) >> 2}{'=XID'[int(r) & 3]}" for r in row[:int(nruns)].astype(np.int64) & 0xFFFF)
 
 
 def binary_search(sa: SaNaive, q, cnt: Counter | None = None) -> int:
