@@ -676,6 +676,75 @@ int sas_align_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t
                          uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs, void* stream,
                          uint32_t flags);
 
+/* Reverse complement of DNA queries: rc(q)[j] = q[m - 1 - j] ^ 3 for a query of m chars (the codes
+ * are A C G T = 0 1 2 3, so the complement of c is c ^ 3).  sas_revcomp writes the reverse
+ * complements of the ragged queries back to back in query order, and out_off[0 .. nq] (u64) = the
+ * exclusive sum of qlen: ragged inputs may overlap in qbytes, so their offsets cannot be reused.
+ * sas_revcomp_fixed writes query i at out_bytes[i m].  The calls take no index; with
+ * SAS_DEVICE_PTRS they run on the current device, asynchronous on `stream`.  Anyone who wants every
+ * hit of sas_locate_edit / sas_locate_mismatch on both strands needs them.  Flags: SAS_DEVICE_PTRS
+ * and SAS_VALIDATE (rejects bytes > 3, synchronises); host pointers: synchronous, bytes always
+ * validated.  nq == 0 writes out_off[0] = 0 and nothing else. */
+int sas_revcomp(const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen, uint64_t nq,
+                uint8_t* out_bytes, uint64_t* out_off, void* stream, uint32_t flags);
+int sas_revcomp_fixed(const uint8_t* qbytes, uint32_t m, uint64_t nq, uint8_t* out_bytes, void* stream,
+                      uint32_t flags);
+
+/* Read mapping: the best alignment of every read on both strands, one fixed-size record per read.
+ * For read i with the query q of m chars, a bound k in 0..15 (EINVAL above) and max_seed_hits:
+ *   - q_0 = q and q_1 = rc(q);
+ *   - A_s is the answer that sas_locate_edit defines for q_s with the same k and max_seed_hits: a
+ *     list of (e, D) ascending in e, empty for a SAS_ED_SHORT or SAS_ED_LONG query, reduced in
+ *     the way documented there when a seed is skipped;
+ *   - `strands` is a bit mask, SAS_MAP_FWD, SAS_MAP_REV or both (EINVAL otherwise): only the
+ *     selected strands take part, and everything below is a pure function of their A_s.
+ * Reported per read:
+ *   - best: the least triple (D, s, e) over all ends of all participating strands, in
+ *     lexicographic order: the least distance, then forward before reverse, then the smallest
+ *     end.  It gives out_dist, out_strand and out_end.  The end is a text coordinate on either
+ *     strand: the reverse-strand alignment is that of rc(q) against t[start .. end), as SAM
+ *     reports it;
+ *   - n_best: the number of maximal intervals e, e + 1, e + 2, ... of consecutive ends, all in A_s
+ *     of one strand and all at the distance out_dist, summed over the strands.  Two occurrences
+ *     two chars apart count as two; one occurrence never counts twice.  A read that equals its
+ *     own reverse complement counts each place once per strand;
+ *   - n_loci: the number of maximal intervals of consecutive reported ends, of any distance <= k,
+ *     summed over the strands.  As |D(e + 1) - D(e)| <= 1 these are the valleys of D below k + 1.
+ *     n_best == 1 && n_loci == 1 is the unique mapping.  Both counts are accumulated in 64 bits
+ *     and written clamped at UINT32_MAX;
+ *   - out_start, out_nruns, out_runs (2k + 1 slots per read): exactly what sas_align_edit defines
+ *     for (q_strand, end, k): the largest start that reaches the distance, its tie rule, its runs;
+ *   - out_qflags: the OR of the SAS_ED_* flags of the participating strands;
+ *   - no end on any participating strand: end = start = n, dist = SAS_AL_NONE_DIST, strand = 0,
+ *     n_best = n_loci = 0, nruns = 0, every run slot 0.
+ * Every output has one entry per read (out_end / out_start u64, or u32 with SAS_LOCATE_U32, which
+ * needs n < 2^32: EINVAL otherwise): there is no capacity, no sizing call and no ENOSPC.  out_start,
+ * out_strand, out_nbest, out_nloci, out_nruns, out_runs and out_qflags may each be NULL; out_end
+ * and out_dist are required when nq > 0.  nq == 0 writes nothing.  Flags: SAS_DEVICE_PTRS,
+ * SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE.  The index requirements and their errors are
+ * those of sas_locate_edit (ENOTSUP for shards, parts and tagged indexes); the reads of both
+ * strands are one batch of the seed-and-verify path, so EINVAL when the bits of 2 nq - 1 and of n
+ * together exceed the 64-bit sort key.  Only each read's winner is aligned, one alignment per read.
+ * With SAS_DEVICE_PTRS: scratch from the index's stream-ordered pool; the call synchronises on
+ * `stream` where sas_locate_edit does, twice (the candidates and the proposed ends of the whole
+ * batch), and, for ragged queries with the reverse strand selected, once more before them, to
+ * size the batch's bytes from the sum of qlen (sas_map_edit_fixed and SAS_MAP_FWD alone: never).
+ * Nothing else synchronises unless SAS_VALIDATE is set.  With host pointers: synchronous, bytes
+ * always validated. */
+#define SAS_MAP_FWD 1u /* strands: the read as given             */
+#define SAS_MAP_REV 2u /* strands: the read's reverse complement */
+int sas_map_edit(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                 uint64_t nq, uint32_t k, uint64_t max_seed_hits, uint32_t strands, void* out_end,
+                 void* out_start, uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest,
+                 uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
+                 void* stream, uint32_t flags);
+/* sas_map_edit for fixed-length reads qbytes[k*m .. (k+1)*m). */
+int sas_map_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
+                       uint64_t max_seed_hits, uint32_t strands, void* out_end, void* out_start,
+                       uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest, uint32_t* out_nloci,
+                       uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags, void* stream,
+                       uint32_t flags);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

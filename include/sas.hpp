@@ -377,6 +377,50 @@ class SaNaive {
         return r;
     }
 
+    /* Result of map_edit, one record per read: the best alignment on the selected strands
+     * (strand 1: the read's reverse complement against t[start .. end)), n_best / n_loci = the
+     * equally good and all places (n_best == 1 && n_loci == 1: the unique mapping), the script as
+     * in Aligned, qflags = SAS_ED_* of the strands.  An unmapped read has end = start = n,
+     * dist = SAS_AL_NONE_DIST and n_best = 0 */
+    struct Mapped {
+        std::vector<uint64_t> end, start;
+        std::vector<uint8_t> dist, strand, nruns, qflags;
+        std::vector<uint32_t> n_best, n_loci;
+        std::vector<uint16_t> runs;
+        size_t stride = 1;
+    };
+
+    /* read mapping in one call (sas_map_edit): every read's best alignment within k edits on both
+     * strands (strands: SAS_MAP_FWD | SAS_MAP_REV), its script and how many places are as good */
+    Mapped map_edit(const std::vector<Seq>& qs, uint32_t k, uint64_t max_seed_hits = 0,
+                    uint32_t strands = SAS_MAP_FWD | SAS_MAP_REV, uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Mapped r;
+        const size_t nq = qs.size();
+        r.stride = 2 * (size_t)k + 1;
+        r.end.assign(nq, n_);
+        r.start.assign(nq, n_);
+        r.dist.assign(nq, (uint8_t)SAS_AL_NONE_DIST);
+        r.strand.assign(nq, 0);
+        r.nruns.assign(nq, 0);
+        r.qflags.assign(nq, 0);
+        r.n_best.assign(nq, 0);
+        r.n_loci.assign(nq, 0);
+        r.runs.assign(nq * r.stride, 0);
+        check(sas_map_edit(h_, bytes.data(), qoff.data(), len.data(), nq, k, max_seed_hits, strands, r.end.data(),
+                           r.start.data(), r.dist.data(), r.strand.data(), r.n_best.data(), r.n_loci.data(),
+                           r.nruns.data(), r.runs.data(), r.qflags.data(), nullptr, flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are

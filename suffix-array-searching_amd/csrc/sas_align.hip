@@ -37,10 +37,6 @@
 #include <algorithm>
 #include <cstring>
 
-#define AL_BLOCK 256
-#define AL_T 1024           // alignments per tile
-#define AL_PER (AL_T / AL_BLOCK)
-#define AL_SLICE 2048       // query offsets of a tile staged in LDS (8 KiB)
 #define AL_BPC 4            // workgroups per CU that size the grid and the scratch
 
 struct AlArgs {
@@ -57,58 +53,6 @@ struct AlArgs {
     uint16_t* out_runs;     // may be null; 2k + 1 slots per alignment
     void* scr;              // direction words, [row][thread of the grid]
 };
-
-// The queries of the alignments [t0, t0 + n_el) of one tile (n_el <= AL_T), for the whole
-// workgroup: element e = u AL_BLOCK + tid belongs to the last query qi[u] with off[qi] <= t0 + e
-// (bisecting the tile's slice of `off`, staged in `rel` when it fits); ok[u] = 0 for an element
-// past the tile or one that fails the offsets' own bounds.  The caller puts a __syncthreads()
-// between two tiles.
-__device__ __forceinline__ void al_tile_queries(const uint64_t* __restrict__ off, uint64_t nq, uint64_t t0,
-                                                uint32_t n_el, uint32_t* rel, uint64_t* sh_p, uint64_t (&qi)[AL_PER],
-                                                uint32_t (&ok)[AL_PER]) {
-    const uint32_t tid = threadIdx.x;
-    // the queries of the tile's first and last alignment (both non-empty)
-    if (tid < 2) sh_p[tid] = mm_piece_of(off, nq, tid ? t0 + n_el - 1 : t0);
-    __syncthreads();
-    const uint64_t p0 = sh_p[0];
-    uint64_t p1 = sh_p[1];
-    if (p1 < p0) p1 = p0;
-    if (p1 > nq - 1) p1 = nq - 1;
-    const uint64_t nps = p1 - p0 + 1;
-    const uint32_t staged = nps <= AL_SLICE ? 1u : 0u;
-    if (staged) {
-        for (uint32_t x = tid; x < (uint32_t)nps; x += AL_BLOCK) {
-            const uint64_t o = off[p0 + x];
-            rel[x] = o <= t0 ? 0u : (o - t0 >= AL_T ? (uint32_t)AL_T : (uint32_t)(o - t0));
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < AL_PER; u++) {
-        const uint32_t e = u * AL_BLOCK + tid;
-        const uint64_t c = t0 + e;
-        ok[u] = e < n_el ? 1u : 0u;
-        qi[u] = 0;
-        if (ok[u]) {
-            uint64_t l = 1, h = nps;
-            if (staged) {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (rel[mid] <= e) l = mid + 1;
-                    else h = mid;
-                }
-            } else {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (off[p0 + mid] <= c) l = mid + 1;
-                    else h = mid;
-                }
-            }
-            qi[u] = p0 + l - 1;
-            ok[u] = (off[qi[u]] <= c && c < off[qi[u] + 1]) ? 1u : 0u;
-        }
-    }
-}
 
 template <int KB> struct AlWord;
 template <> struct AlWord<1> { typedef uint8_t type; };

@@ -38,7 +38,7 @@
 //                      (out_off[q] = unique keys below query q, by bisection) and k_ed_scatter
 //                      (out_end / out_dist, bounded by capacity).  Equal keys carry equal
 //                      distances, so which duplicate is kept does not matter.
-#include "seed_verify.hpp"
+#include "edit_path.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -301,25 +301,9 @@ extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
     return ed_last_dedup_ms;
 }
 
-static uint32_t ed_bits(uint64_t v) {  // bits that hold every value in [0, v]
-    uint32_t b = 1;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
-
 struct EdEvent {  // destroyed on every way out
     hipEvent_t e = nullptr;
     ~EdEvent() { if (e) (void)hipEventDestroy(e); }
-};
-
-// Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
-struct EdState {
-    hipMemPool_t pool = nullptr;
-    MmPoolBuf poff, plen, lohi, coff, qfl, mask, kbase, dists, pscan, keys, vals, uscan;
-    const uint64_t* skeys = nullptr;  // the sorted proposals
-    const uint8_t* svals = nullptr;
-    uint64_t C = 0, P = 0;
-    uint32_t ebits = 0;
 };
 
 template <int NW>
@@ -329,9 +313,9 @@ static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, cons
 }
 
 // All arrays on the device (out_total may be null).  Two host reads: the candidate total and
-// the proposal total
-static int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off,
-                      uint8_t* out_qflags, uint64_t* out_total, hipStream_t st, uint32_t flags, EdState& s) {
+// the proposal total (edit_path.hpp)
+int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off,
+               uint8_t* out_qflags, uint64_t* out_total, hipStream_t st, uint32_t flags, EdState& s) {
     const uint32_t kp1 = k + 1;
     const uint64_t nq = Q.nq, np = nq * kp1;
     s.ebits = ed_bits(x->n);

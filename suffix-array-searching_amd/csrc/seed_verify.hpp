@@ -1,7 +1,8 @@
 // seed_verify.hpp -- what the seed-and-verify calls share (sas_mismatch.hip: Hamming distance,
 // sas_edit.hip: edit distance): the query batch as the kernels see it, the cut of a query into
 // k + 1 pieces, the output-centric tiling of the candidates (one candidate = one occurrence of
-// one piece), stream-ordered scratch and a scan helper.
+// one piece) and of the elements of a CSR list (sas_align.hip: alignments, sas_map.hip: the bytes
+// of a ragged batch), stream-ordered scratch and a scan helper.
 #pragma once
 #include "build_util.hpp"
 
@@ -112,6 +113,63 @@ __device__ __forceinline__ void mm_tile_candidates(const SA& sa, const uint64_t*
     }
 #pragma unroll
     for (int u = 0; u < MM_PER; u++) pv[u] = ok[u] ? sa[rk[u]] : 0;
+}
+
+#define AL_BLOCK 256
+#define AL_T 1024           // elements per tile
+#define AL_PER (AL_T / AL_BLOCK)
+#define AL_SLICE 2048       // query offsets of a tile staged in LDS (8 KiB)
+
+// The queries of the elements [t0, t0 + n_el) of one tile of a CSR list (n_el <= AL_T; off: its
+// nq + 1 offsets), for the whole workgroup of AL_BLOCK threads: element e = u AL_BLOCK + tid
+// belongs to the last query qi[u] with off[qi] <= t0 + e (bisecting the tile's slice of `off`,
+// staged in `rel` when it fits); ok[u] = 0 for an element past the tile or one that fails the
+// offsets' own bounds.  The caller puts a __syncthreads() between two tiles.
+__device__ __forceinline__ void al_tile_queries(const uint64_t* __restrict__ off, uint64_t nq, uint64_t t0,
+                                                uint32_t n_el, uint32_t* rel, uint64_t* sh_p, uint64_t (&qi)[AL_PER],
+                                                uint32_t (&ok)[AL_PER]) {
+    const uint32_t tid = threadIdx.x;
+    // the queries of the tile's first and last element (both non-empty)
+    if (tid < 2) sh_p[tid] = mm_piece_of(off, nq, tid ? t0 + n_el - 1 : t0);
+    __syncthreads();
+    const uint64_t p0 = sh_p[0];
+    uint64_t p1 = sh_p[1];
+    if (p1 < p0) p1 = p0;
+    if (p1 > nq - 1) p1 = nq - 1;
+    const uint64_t nps = p1 - p0 + 1;
+    const uint32_t staged = nps <= AL_SLICE ? 1u : 0u;
+    if (staged) {
+        for (uint32_t x = tid; x < (uint32_t)nps; x += AL_BLOCK) {
+            const uint64_t o = off[p0 + x];
+            rel[x] = o <= t0 ? 0u : (o - t0 >= AL_T ? (uint32_t)AL_T : (uint32_t)(o - t0));
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < AL_PER; u++) {
+        const uint32_t e = u * AL_BLOCK + tid;
+        const uint64_t c = t0 + e;
+        ok[u] = e < n_el ? 1u : 0u;
+        qi[u] = 0;
+        if (ok[u]) {
+            uint64_t l = 1, h = nps;
+            if (staged) {
+                while (l < h) {
+                    const uint64_t mid = (l + h) >> 1;
+                    if (rel[mid] <= e) l = mid + 1;
+                    else h = mid;
+                }
+            } else {
+                while (l < h) {
+                    const uint64_t mid = (l + h) >> 1;
+                    if (off[p0 + mid] <= c) l = mid + 1;
+                    else h = mid;
+                }
+            }
+            qi[u] = p0 + l - 1;
+            ok[u] = (off[qi[u]] <= c && c < off[qi[u] + 1]) ? 1u : 0u;
+        }
+    }
 }
 
 struct MmPoolBuf {  // stream-ordered scratch from the index's pool

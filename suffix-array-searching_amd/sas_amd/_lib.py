@@ -40,6 +40,8 @@ SAS_AL_X = 1
 SAS_AL_INS = 2
 SAS_AL_DEL = 3
 SAS_AL_NONE_DIST = 255
+SAS_MAP_FWD = 1  # sas_map_edit's strands mask
+SAS_MAP_REV = 2
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
 SAS_BUILD_SA40 = 1 << 8
@@ -192,6 +194,10 @@ def lib():
     L.sas_locate_edit_dedup_ms.restype = C.c_double
     L.sas_align_edit.argtypes = [vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, u32]
     L.sas_align_edit_fixed.argtypes = [vp, vp, u32, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, u32]
+    L.sas_revcomp.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32]
+    L.sas_revcomp_fixed.argtypes = [vp, u32, u64, vp, vp, u32]
+    L.sas_map_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32]
+    L.sas_map_edit_fixed.argtypes = [vp, vp, u32, u64, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import errno
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -26,6 +27,10 @@ from ._lib import check, lib
 class Counter:
     """Stands in for the reference's `cnt: &mut usize` argument."""
     value: int = 0
+
+
+# one record per read of SaNaive.map_edit (sas_map_edit)
+Mapped = namedtuple("Mapped", "end start dist strand n_best n_loci nruns runs qflags")
 
 
 def _is_cuda(x) -> bool:
@@ -883,6 +888,69 @@ class SaNaive:
         nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
         return self._align_edit(qbytes, None, None, int(m), nq, k, off, end, u32, stream, flags)
 
+    # -- read mapping: the best alignment per read on both strands (sas_map_edit*)
+    def _map_edit(self, qbytes, qoff, qlen, m, nq, k, max_seed_hits, strands, u32, stream, flags):
+        L = lib()
+        k = int(k)
+        stride = 2 * k + 1
+
+        def call(r, st, fl):
+            tail = (k, int(max_seed_hits), int(strands), _ptr(r.end), _ptr(r.start), _ptr(r.dist), _ptr(r.strand),
+                    _ptr(r.n_best), _ptr(r.n_loci), _ptr(r.nruns), _ptr(r.runs), _ptr(r.qflags), st, fl)
+            if qoff is not None:
+                return L.sas_map_edit(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, *tail)
+            return L.sas_map_edit_fixed(self._h, _ptr(qbytes), m, nq, *tail)
+
+        if _is_cuda(qbytes):
+            import torch
+            d = qbytes.device
+            dt = torch.int32 if u32 else torch.int64
+            st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+            fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+
+            def new(shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=d)
+            r = Mapped(new(nq, dt), new(nq, dt), new(nq, torch.uint8), new(nq, torch.uint8), new(nq, torch.int32),
+                       new(nq, torch.int32), new(nq, torch.uint8), new((nq, stride), torch.int16),
+                       new(nq, torch.uint8))
+            check(call(r, st, fl))
+            return r
+        qbytes = _as_u8(qbytes)
+        pt = np.uint32 if u32 else np.uint64
+        r = Mapped(np.empty(nq, pt), np.empty(nq, pt), np.empty(nq, np.uint8), np.empty(nq, np.uint8),
+                   np.empty(nq, np.uint32), np.empty(nq, np.uint32), np.empty(nq, np.uint8),
+                   np.empty((nq, stride), np.uint16), np.empty(nq, np.uint8))
+        check(call(r, stream, flags | (_lib.SAS_LOCATE_U32 if u32 else 0)))
+        return r
+
+    def map_edit(self, qbytes, qoff, qlen, k: int, max_seed_hits: int = 0, strands: int = 3, u32: bool = False,
+                 flags: int = 0, stream=None):
+        """Read mapping (sas_map_edit): one record per ragged read qbytes[qoff[i] : qoff[i] + qlen[i]],
+        the named tuple Mapped(end, start, dist, strand, n_best, n_loci, nruns, runs, qflags).  Over
+        the ends locate_edit defines for the read (strand 0) and for its reverse complement (strand 1)
+        at the same k and max_seed_hits, the best is the least (dist, strand, end); the strand-1
+        alignment is that of the reverse complement against t[start : end].  n_best counts the
+        maximal runs of consecutive ends at the best distance, n_loci those of any distance <= k,
+        both summed over the strands (n_best == 1 and n_loci == 1: the unique mapping); start, nruns
+        and runs (2k + 1 columns) are align_edit's for the winner; qflags is the OR of the strands'
+        SAS_ED_* flags.  strands: 1 forward only, 2 reverse only, 3 both.  An unmapped read has
+        end = start = n, dist = 255, strand = 0 and zero counts and runs.  numpy in -> numpy out;
+        torch CUDA in -> CUDA out (n_best / n_loci as int32, runs as int16 bit patterns)."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._map_edit(qbytes, qoff, qlen, 0, nq, k, max_seed_hits, strands, u32, stream, flags)
+
+    def map_edit_fixed(self, qbytes, m: int, k: int, max_seed_hits: int = 0, strands: int = 3, u32: bool = False,
+                       flags: int = 0, stream=None):
+        """map_edit for fixed-length reads qbytes[i*m : (i+1)*m] (sas_map_edit_fixed)."""
+        if m <= 0:
+            raise ValueError("use map_edit for empty reads")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._map_edit(qbytes, None, None, int(m), nq, k, max_seed_hits, strands, u32, stream, flags)
+
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
         kn, cn = C.c_double(0), C.c_double(0)
@@ -897,6 +965,46 @@ def cigar(runs_row, nruns) -> str:
     a text char that the query lacks."""
     row = runs_row.cpu().numpy() if hasattr(runs_row, "cpu") else np.asarray(runs_row)
     return "".join(f"{int(r) >> 2}{'=XID'[int(r) & 3]}" for r in row[:int(nruns)].astype(np.int64) & 0xFFFF)
+
+
+def revcomp(qbytes, qoff=None, qlen=None, m: int | None = None, stream=None, flags: int = 0):
+    """Reverse complements of DNA queries, rc(q)[j] = q[len - 1 - j] ^ 3 (sas_revcomp): for ragged
+    queries qbytes[qoff[i] : qoff[i] + qlen[i]] (which may overlap) -> (bytes, off), the reverse
+    complements back to back in query order and off = the exclusive sum of qlen (nq + 1 entries);
+    with m, for fixed-length queries qbytes[i*m : (i+1)*m] -> bytes, query i at i*m
+    (sas_revcomp_fixed).  numpy in -> numpy out (bytes validated); torch CUDA in -> CUDA out, on
+    the current stream of the tensor's device."""
+    L = lib()
+    dev = _is_cuda(qbytes)
+    if dev:
+        import torch
+        d = qbytes.device
+        st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+        fl = flags | _lib.SAS_DEVICE_PTRS
+        with torch.cuda.device(d):
+            if m is not None:
+                nq = qbytes.numel() // int(m)
+                out = torch.empty(nq * int(m), dtype=torch.uint8, device=d)
+                check(L.sas_revcomp_fixed(_ptr(qbytes), int(m), nq, _ptr(out), st, fl))
+                return out
+            nq = int(qoff.numel())
+            out = torch.empty(int(qlen.sum()) if nq else 0, dtype=torch.uint8, device=d)
+            off = torch.empty(nq + 1, dtype=torch.int64, device=d)
+            check(L.sas_revcomp(_ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, _ptr(out), _ptr(off), st, fl))
+            return out, off
+    qbytes = _as_u8(qbytes)
+    if m is not None:
+        nq = len(qbytes) // int(m)
+        out = np.empty(nq * int(m), np.uint8)
+        check(L.sas_revcomp_fixed(_ptr(qbytes), int(m), nq, _ptr(out), stream, flags))
+        return out
+    qoff = np.ascontiguousarray(qoff, np.uint64)
+    qlen = np.ascontiguousarray(qlen, np.uint32)
+    nq = len(qoff)
+    out = np.empty(int(qlen.astype(np.uint64).sum()), np.uint8)
+    off = np.empty(nq + 1, np.uint64)
+    check(L.sas_revcomp(_ptr(qbytes), _ptr(qoff), _ptr(qlen), nq, _ptr(out), _ptr(off), stream, flags))
+    return out, off
 
 
 def binary_search(sa: SaNaive, q, cnt: Counter | None = None) -> int:
