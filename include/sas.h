@@ -745,6 +745,69 @@ int sas_map_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m
                        uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags, void* stream,
                        uint32_t flags);
 
+/* Paired-end mapping: the reads of a pair placed together, by a join of their ends on the fragment
+ * length.  One batch of 2 np reads, interleaved as in an interleaved FASTQ: pair i is read 2i
+ * (mate 1) and read 2i + 1 (mate 2); the query arguments are those of sas_map_edit / _fixed with
+ * nq = 2 np.  k is 0..15 (EINVAL above), max_seed_hits as there, min_frag <= max_frag.
+ *   - answers: for read r, A_0(r) and A_1(r) are exactly sas_map_edit's: the sas_locate_edit answer
+ *     of the read and of its reverse complement for the same k and max_seed_hits, empty for a
+ *     SAS_ED_SHORT or SAS_ED_LONG read, reduced as documented there when a seed is skipped;
+ *   - loci: a locus of (r, s) is a maximal interval e, e + 1, e + 2, ... of consecutive ends in
+ *     A_s(r), the intervals n_loci counts.  Its representative is the least (D, e) in it, in
+ *     lexicographic order;
+ *   - candidates: the orientation is forward / reverse (the Illumina paired-end library) and is
+ *     fixed.  For orientation o in {0, 1} the forward mate is f = 2i + o and the reverse mate is
+ *     v = 2i + 1 - o; a candidate is (x, y), x a locus of (f, 0) and y a locus of (v, 1), with the
+ *     representatives (D_x, e_x) and (D_y, e_y);
+ *   - fragment length: F = e_y - e_x + m_f in signed 64-bit arithmetic, m_f the forward mate's
+ *     length: the template length with the forward mate's start taken as e_x - m_f.  The true one,
+ *     end_v - start_f of the outputs, differs from it by at most k; using ends alone keeps the join
+ *     a pure function of the A_s.  The candidate is proper iff min_frag <= F <= max_frag.
+ * Reported per pair (np entries each):
+ *   - out_npairs: the number of proper candidates over both orientations;
+ *   - out_nbestpairs: the number of those with the least sum D_x + D_y;
+ *   - out_pflags: bit SAS_PAIR_PROPER is set iff n_pairs > 0.
+ *     Both counts are accumulated in 64 bits and written clamped at UINT32_MAX;
+ *   - the best pair is the least (D_x + D_y, o, e_x, e_y), in lexicographic order.
+ * Reported per read (2 np entries each, in the layout of sas_map_edit's outputs):
+ *   - in a proper pair read f gets end = e_x, dist = D_x, strand = 0 and read v gets end = e_y,
+ *     dist = D_y, strand = 1; out_start, out_nruns and the 2k + 1 run slots are sas_align_edit's
+ *     for (q_strand, end, k);
+ *   - in a pair that is not proper both reads get exactly the record sas_map_edit gives them with
+ *     strands = SAS_MAP_FWD | SAS_MAP_REV (an unmapped read the unmapped record defined there);
+ *   - out_nbest, out_nloci and out_qflags are always sas_map_edit's single-read values, proper or
+ *     not.
+ * max_frag - min_frag above SAS_PAIR_MAX_SPREAD, or min_frag > max_frag, is EINVAL, checked before
+ * the index: a forward locus's partners lie in a window of spread + 1 end positions, loci are at
+ * least 2 apart, so the window holds at most spread / 2 + 1 of them, which bounds one work item's
+ * scan (and lets the join's key hold e_y relative to the window in 16 bits).  The index
+ * requirements and their errors are sas_map_edit's (ENOTSUP for shards, parts and tagged
+ * indexes); the two mates on two strands are one batch of the seed-and-verify path, so EINVAL
+ * when the bits of 4 np - 1 and of n together exceed the 64-bit sort key.  np == 0 writes
+ * nothing.  out_end and out_dist are required, every other output may be NULL.  Flags:
+ * SAS_DEVICE_PTRS, SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE.  Other orientations (FF,
+ * RF), the rescue of a mate that has no end within k, a mapping quality and SAM text are not
+ * part of the call.
+ * With SAS_DEVICE_PTRS the call synchronises on `stream` where sas_map_edit on the same reads
+ * does, and nowhere else: the loci scratch and the join's grids are sized from the number of
+ * proposed ends, which the host holds already, and the number of loci stays on the device.  With
+ * host pointers: synchronous, bytes always validated. */
+#define SAS_PAIR_PROPER 1u /* out_pflags: some candidate has its fragment length in the window */
+#define SAS_PAIR_MAX_SPREAD 65535u
+int sas_map_pairs(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                  uint64_t npairs, uint32_t k, uint64_t max_seed_hits, uint32_t min_frag, uint32_t max_frag,
+                  void* out_end, void* out_start, uint8_t* out_dist, uint8_t* out_strand,
+                  uint32_t* out_nbest, uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs,
+                  uint8_t* out_qflags, uint8_t* out_pflags, uint32_t* out_npairs, uint32_t* out_nbestpairs,
+                  void* stream, uint32_t flags);
+/* sas_map_pairs for fixed-length reads qbytes[k*m .. (k+1)*m). */
+int sas_map_pairs_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t npairs, uint32_t k,
+                        uint64_t max_seed_hits, uint32_t min_frag, uint32_t max_frag, void* out_end,
+                        void* out_start, uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest,
+                        uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
+                        uint8_t* out_pflags, uint32_t* out_npairs, uint32_t* out_nbestpairs, void* stream,
+                        uint32_t flags);
+
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself
  * (HIP events on `stream`) in *kernel_ns and of the whole call in *call_ns. */

@@ -421,6 +421,52 @@ class SaNaive {
         return r;
     }
 
+    /* Result of map_pairs: Mapped's fields, one entry per read (pair i = reads 2i and 2i + 1), and
+     * per pair pflags (SAS_PAIR_PROPER), n_pairs = the proper candidates and n_best_pairs = those
+     * of the least summed distance */
+    struct MappedPairs : Mapped {
+        std::vector<uint8_t> pflags;
+        std::vector<uint32_t> n_pairs, n_best_pairs;
+    };
+
+    /* paired-end mapping in one call (sas_map_pairs): qs holds the pairs interleaved, mate 1 then
+     * mate 2 (an odd number of reads throws std::invalid_argument); a pair with a forward / reverse
+     * placement whose fragment length is in [min_frag, max_frag] gets that placement, every other
+     * read its own map_edit record */
+    MappedPairs map_pairs(const std::vector<Seq>& qs, uint32_t k, uint32_t min_frag, uint32_t max_frag,
+                          uint64_t max_seed_hits = 0, uint32_t flags = 0) const {
+        if (qs.size() % 2) throw std::invalid_argument("map_pairs: an odd number of reads");
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        MappedPairs r;
+        const size_t nq = qs.size(), np = nq / 2;
+        r.stride = 2 * (size_t)k + 1;
+        r.end.assign(nq, n_);
+        r.start.assign(nq, n_);
+        r.dist.assign(nq, (uint8_t)SAS_AL_NONE_DIST);
+        r.strand.assign(nq, 0);
+        r.nruns.assign(nq, 0);
+        r.qflags.assign(nq, 0);
+        r.n_best.assign(nq, 0);
+        r.n_loci.assign(nq, 0);
+        r.runs.assign(nq * r.stride, 0);
+        r.pflags.assign(np, 0);
+        r.n_pairs.assign(np, 0);
+        r.n_best_pairs.assign(np, 0);
+        check(sas_map_pairs(h_, bytes.data(), qoff.data(), len.data(), np, k, max_seed_hits, min_frag, max_frag,
+                            r.end.data(), r.start.data(), r.dist.data(), r.strand.data(), r.n_best.data(),
+                            r.n_loci.data(), r.nruns.data(), r.runs.data(), r.qflags.data(), r.pflags.data(),
+                            r.n_pairs.data(), r.n_best_pairs.data(), nullptr, flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are

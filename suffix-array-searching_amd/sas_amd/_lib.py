@@ -42,6 +42,8 @@ SAS_AL_DEL = 3
 SAS_AL_NONE_DIST = 255
 SAS_MAP_FWD = 1  # sas_map_edit's strands mask
 SAS_MAP_REV = 2
+SAS_PAIR_PROPER = 1  # sas_map_pairs' per-pair flags
+SAS_PAIR_MAX_SPREAD = 65535  # the largest max_frag - min_frag
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
 SAS_BUILD_SA40 = 1 << 8
@@ -198,6 +200,8 @@ def lib():
     L.sas_revcomp_fixed.argtypes = [vp, u32, u64, vp, vp, u32]
     L.sas_map_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32]
     L.sas_map_edit_fixed.argtypes = [vp, vp, u32, u64, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32]
+    L.sas_map_pairs.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u32] + [vp] * 13 + [u32]
+    L.sas_map_pairs_fixed.argtypes = [vp, vp, u32, u64, u32, u64, u32, u32] + [vp] * 13 + [u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

@@ -31,6 +31,8 @@ class Counter:
 
 # one record per read of SaNaive.map_edit (sas_map_edit)
 Mapped = namedtuple("Mapped", "end start dist strand n_best n_loci nruns runs qflags")
+# SaNaive.map_pairs (sas_map_pairs): Mapped's fields per read, then three per pair
+MappedPairs = namedtuple("MappedPairs", Mapped._fields + ("pflags", "n_pairs", "n_best_pairs"))
 
 
 def _is_cuda(x) -> bool:
@@ -950,6 +952,75 @@ class SaNaive:
             raise ValueError("use map_edit for empty reads")
         nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
         return self._map_edit(qbytes, None, None, int(m), nq, k, max_seed_hits, strands, u32, stream, flags)
+
+    # -- paired-end mapping: the mates of a pair placed together (sas_map_pairs*)
+    def _map_pairs(self, qbytes, qoff, qlen, m, nq, k, min_frag, max_frag, max_seed_hits, u32, stream, flags):
+        if nq % 2:
+            raise ValueError(f"paired reads come interleaved, mate 1 then mate 2: {nq} reads is an odd number")
+        L = lib()
+        k = int(k)
+        np_, stride = nq // 2, 2 * k + 1
+
+        def call(r, st, fl):
+            tail = (k, int(max_seed_hits), int(min_frag), int(max_frag)) + tuple(_ptr(v) for v in r) + (st, fl)
+            if qoff is not None:
+                return L.sas_map_pairs(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), np_, *tail)
+            return L.sas_map_pairs_fixed(self._h, _ptr(qbytes), m, np_, *tail)
+
+        if _is_cuda(qbytes):
+            import torch
+            d = qbytes.device
+            dt = torch.int32 if u32 else torch.int64
+            st = stream if stream is not None else torch.cuda.current_stream(d).cuda_stream
+            fl = flags | _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)
+
+            def new(shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=d)
+            r = MappedPairs(new(nq, dt), new(nq, dt), new(nq, torch.uint8), new(nq, torch.uint8),
+                            new(nq, torch.int32), new(nq, torch.int32), new(nq, torch.uint8),
+                            new((nq, stride), torch.int16), new(nq, torch.uint8), new(np_, torch.uint8),
+                            new(np_, torch.int32), new(np_, torch.int32))
+            check(call(r, st, fl))
+            return r
+        qbytes = _as_u8(qbytes)
+        pt = np.uint32 if u32 else np.uint64
+        r = MappedPairs(np.empty(nq, pt), np.empty(nq, pt), np.empty(nq, np.uint8), np.empty(nq, np.uint8),
+                        np.empty(nq, np.uint32), np.empty(nq, np.uint32), np.empty(nq, np.uint8),
+                        np.empty((nq, stride), np.uint16), np.empty(nq, np.uint8), np.empty(np_, np.uint8),
+                        np.empty(np_, np.uint32), np.empty(np_, np.uint32))
+        check(call(r, stream, flags | (_lib.SAS_LOCATE_U32 if u32 else 0)))
+        return r
+
+    def map_pairs(self, qbytes, qoff, qlen, k: int, min_frag: int, max_frag: int, max_seed_hits: int = 0,
+                  u32: bool = False, flags: int = 0, stream=None):
+        """Paired-end mapping (sas_map_pairs): the ragged reads come interleaved, pair i = reads 2i
+        (mate 1) and 2i + 1 (mate 2); an odd number of reads raises ValueError.  Returns the named
+        tuple MappedPairs(end, start, dist, strand, n_best, n_loci, nruns, runs, qflags, pflags,
+        n_pairs, n_best_pairs): the first nine as map_edit's, one entry per read, the last three one
+        entry per pair.  A candidate is a locus (a maximal run of consecutive ends, represented by
+        its least (dist, end)) of one mate on the forward strand with one of the other mate on the
+        reverse strand; it is proper when min_frag <= e_rev - e_fwd + len(forward mate) <= max_frag
+        (max_frag - min_frag <= 65535).  n_pairs counts the proper candidates, n_best_pairs those of
+        the least summed distance, pflags bit 0 (SAS_PAIR_PROPER) says there is one.  In a proper
+        pair both reads get the best candidate's ends (the least (sum, orientation, forward end,
+        reverse end)), strands 0 / 1 and align_edit's start and runs for them; otherwise each read
+        keeps map_edit's own record.  n_best, n_loci and qflags are always map_edit's.  numpy in ->
+        numpy out; torch CUDA in -> CUDA out (counts as int32, runs as int16 bit patterns)."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._map_pairs(qbytes, qoff, qlen, 0, nq, k, min_frag, max_frag, max_seed_hits, u32, stream, flags)
+
+    def map_pairs_fixed(self, qbytes, m: int, k: int, min_frag: int, max_frag: int, max_seed_hits: int = 0,
+                        u32: bool = False, flags: int = 0, stream=None):
+        """map_pairs for fixed-length reads qbytes[i*m : (i+1)*m] (sas_map_pairs_fixed)."""
+        if m <= 0:
+            raise ValueError("use map_pairs for empty reads")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._map_pairs(qbytes, None, None, int(m), nq, k, min_frag, max_frag, max_seed_hits, u32, stream,
+                               flags)
 
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
