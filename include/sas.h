@@ -622,6 +622,12 @@ int sas_locate_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_
  * figures in ms (< 0: none), with the candidates verified and the ends proposed. */
 double sas_locate_edit_verify_ms(uint64_t* candidates);
 double sas_locate_edit_dedup_ms(uint64_t* proposals);
+/* Debug helper for tests: SAS_TILE_GRID=g in the environment (read at every call) caps at g
+ * workgroups the grids of the tiled kernels of sas_locate*, sas_locate_mismatch*,
+ * sas_locate_edit*, sas_align_edit*, sas_map_edit*, sas_map_pairs* and sas_revcomp*, so a small
+ * batch takes the tile loops of a large one; results do not depend on it.  It only lowers a
+ * grid.  This returns the cap in force, 0 for none (unset, empty or not positive). */
+uint32_t sas_tile_grid_cap(void);
 
 /* Where an approximate match starts and its edit script, for ends that sas_locate_edit*
  * reported (or any other ends).  For a query q of m chars, an end e in [0, n] and a bound k in

@@ -3,11 +3,31 @@
 #pragma once
 #include "common.hpp"
 
+#include <cstdlib>
+
 static inline unsigned grid_for(uint64_t count, unsigned block = 256) {
     uint64_t g = (count + block - 1) / block;
     if (g < 1) g = 1;
     if (g > 262144) g = 262144;  // grid-stride beyond
     return (unsigned)g;
+}
+
+// debug: SAS_TILE_GRID=g caps at g workgroups the grid of every output-centric tiled kernel
+// (k_locate_fill, k_mm_verify, k_ed_verify, k_al_align, k_map_fill, k_map_select, k_pair_heads,
+// k_pair_loci, k_pair_join) and of the grid(count) helpers of their calls, so a small batch takes
+// the tile loop that a large one needs: g = 1 hands every tile to one workgroup in turn
+// (tests/test_gpu_tiles.py).  Read at every call; it only ever lowers a grid: unset, empty or
+// non-positive is no cap.  sas_tile_grid_cap (sas.h) returns the cap in force, 0 for none
+static inline uint32_t tile_grid_cap() {
+    const char* e = getenv("SAS_TILE_GRID");
+    if (!e) return 0;
+    const long long v = atoll(e);
+    return v <= 0 ? 0u : (v > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)v);
+}
+template <class G>
+static inline G tile_grid(G blocks) {
+    const uint32_t cap = tile_grid_cap();
+    return cap && (uint64_t)cap < (uint64_t)blocks ? (G)cap : blocks;
 }
 
 #define GRID_STRIDE(i, count) \

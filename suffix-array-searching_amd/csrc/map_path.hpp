@@ -275,7 +275,7 @@ struct MapState {
     hipMemPool_t pool;
     TRY(sas_scratch_pool(x, &pool));
     const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     // 1. the batch
     MmQueries& B = ms.B;
     B = Q;
@@ -299,9 +299,10 @@ struct MapState {
             HIP_TRY(hipGetLastError());
             const uint64_t tiles = (copies * total + AL_T - 1) / AL_T;
             if (tiles) {
-                hipLaunchKernelGGL(k_map_fill, dim3((unsigned)std::min<uint64_t>(tiles, cap_grid)), dim3(AL_BLOCK), 0, st,
-                                   Q.qbytes, Q.qoff, Q.qlen, nq, ms.boff.as<uint64_t>(), nb, copies == 2 ? nq : 0,
-                                   ms.bbytes.as<uint8_t>(), (uint32_t*)nullptr);
+                const dim3 fgrid((unsigned)tile_grid(std::min<uint64_t>(tiles, cap_grid)));
+                hipLaunchKernelGGL(k_map_fill, fgrid, dim3(AL_BLOCK), 0, st, Q.qbytes, Q.qoff, Q.qlen, nq,
+                                   ms.boff.as<uint64_t>(), nb, copies == 2 ? nq : 0, ms.bbytes.as<uint8_t>(),
+                                   (uint32_t*)nullptr);
                 HIP_TRY(hipGetLastError());
             }
             B.qbytes = ms.bbytes.as<uint8_t>();
@@ -345,7 +346,7 @@ struct MapState {
         a.nloci = ms.nloci;
         a.nbest = ms.nbest;
         const uint64_t tiles = (s.P + MAP_T - 1) / MAP_T;
-        const dim3 sgrid((unsigned)std::min<uint64_t>(tiles, (uint64_t)x->num_cus * MAP_BPC));
+        const dim3 sgrid((unsigned)tile_grid(std::min<uint64_t>(tiles, (uint64_t)x->num_cus * MAP_BPC)));
         hipLaunchKernelGGL(k_map_select<1>, sgrid, dim3(MAP_BLOCK), 0, st, a);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_map_select<2>, sgrid, dim3(MAP_BLOCK), 0, st, a);

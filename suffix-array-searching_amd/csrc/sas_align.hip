@@ -261,13 +261,14 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
         TRY(bflag.alloc(4, "align flag"));
         HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
         const uint64_t total = Q.qoff ? Q.nq : Q.nq * (uint64_t)Q.m;
-        hipLaunchKernelGGL(k_al_validate, dim3(grid_for(total)), dim3(256), 0, st, Q.qbytes, Q.qoff, Q.qlen, Q.nq,
-                           total, bflag.as<uint32_t>());
+        hipLaunchKernelGGL(k_al_validate, dim3(tile_grid(grid_for(total))), dim3(256), 0, st, Q.qbytes, Q.qoff, Q.qlen,
+                           Q.nq, total, bflag.as<uint32_t>());
         HIP_TRY(hipGetLastError());
     }
     uint64_t blocks = (na + AL_T - 1) / AL_T;
     const uint64_t capb = (uint64_t)x->num_cus * AL_BPC;
     if (blocks > capb) blocks = capb;
+    blocks = tile_grid(blocks);  // before the scratch is sized from it
     const uint32_t kb = k <= 1 ? 1u : (k <= 3 ? 3u : (k <= 7 ? 7u : 15u));
     const uint32_t wbytes = kb == 1 ? 1u : (kb == 3 ? 2u : (kb == 7 ? 4u : 8u));
     // direction words: one per row of the longest query that is served, per thread of the grid

@@ -331,7 +331,7 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     uint64_t* lo = s.lohi.as<uint64_t>();
     uint64_t* hi = lo + np;
     const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     const auto nothing = [&]() {
         HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
         if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
@@ -372,7 +372,7 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     a.dists = s.dists.as<ulonglong2>();
     uint64_t blocks = (C + MM_T - 1) / MM_T;
     if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
-    const dim3 vgrid((unsigned)blocks);
+    const dim3 vgrid((unsigned)tile_grid(blocks));
     EdEvent ev0, ev1;
     const bool timing = ed_timing();
     if (timing) {

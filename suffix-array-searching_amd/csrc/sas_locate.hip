@@ -228,6 +228,8 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_locate_fill(SA sa, uint64_t sa_n,
     }
 }
 
+extern "C" uint32_t sas_tile_grid_cap(void) { return tile_grid_cap(); }
+
 static int locate_checks(const char* fn, const sas_index* x, uint32_t flags) {
     if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
         SAS_FAIL(EINVAL, std::string(fn) + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
@@ -304,7 +306,7 @@ extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uin
     // workgroups they stride.  Workgroups whose tile starts past the total exit at once
     uint64_t blocks = ntiles;
     if (blocks > LOC_MAX_GRID) blocks = LOC_MAX_GRID;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)tile_grid(blocks));
     const bool u32 = (flags & SAS_LOCATE_U32) != 0;
     if (x->tag_lines)
         launch_fill(u32, grid, st, TlView{x->tag_lines, x->tag_ovf, x->tag_first, 1ull << (2 * x->tag_p), x->tag_sb}, x,

@@ -93,7 +93,7 @@ static int map_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     hipMemPool_t pool;
     TRY(sas_scratch_pool(x, &pool));
     const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     // 1..3. the batch, its sorted proposals, the slots (map_path.hpp)
     MapState ms;
     TRY(map_select_batch(x, Q, k, max_seed_hits, strands, st, flags, ms));
@@ -241,11 +241,11 @@ static int revcomp_device(const char* fn, const uint8_t* q, const uint64_t* qoff
                     rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), MapLenAt{qlen, nq}),
                     out_off, nq + 1));
         // the grid does not wait for the byte total: the tiles are strided over it
-        hipLaunchKernelGGL(k_map_fill, dim3(cap_grid), dim3(AL_BLOCK), 0, st, q, qoff, qlen,
+        hipLaunchKernelGGL(k_map_fill, dim3(tile_grid(cap_grid)), dim3(AL_BLOCK), 0, st, q, qoff, qlen,
                            nq, out_off, nq, (uint64_t)0, out, bflag.as<uint32_t>());
     } else {
-        hipLaunchKernelGGL(k_map_revcomp_fixed, dim3(std::min(grid_for(nq * (uint64_t)m), cap_grid)), dim3(256), 0, st,
-                           q, m, nq, out, bflag.as<uint32_t>());
+        hipLaunchKernelGGL(k_map_revcomp_fixed, dim3(tile_grid(std::min(grid_for(nq * (uint64_t)m), cap_grid))),
+                           dim3(256), 0, st, q, m, nq, out, bflag.as<uint32_t>());
     }
     HIP_TRY(hipGetLastError());
     if (validate) {

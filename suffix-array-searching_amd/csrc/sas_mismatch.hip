@@ -243,7 +243,7 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     uint64_t* lo = s.lohi.as<uint64_t>();
     uint64_t* hi = lo + np;
     const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     hipLaunchKernelGGL(k_mm_pieces, grid(np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(), s.plen.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
@@ -299,7 +299,7 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     a.cpos = s.cpos.as<uint64_t>();
     uint64_t blocks = (C + MM_T - 1) / MM_T;
     if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
-    const dim3 vgrid((unsigned)blocks);
+    const dim3 vgrid((unsigned)tile_grid(blocks));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timing = mm_timing();
     if (timing) {

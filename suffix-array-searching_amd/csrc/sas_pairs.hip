@@ -436,7 +436,7 @@ static int pairs_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint
     hipMemPool_t pool;
     TRY(sas_scratch_pool(x, &pool));
     const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(std::min(grid_for(count), cap_grid)); };
+    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     // 1. the batch of both strands, its sorted proposals, the single-read slots
     MapState ms;
     TRY(map_select_batch(x, Q, k, max_seed_hits, SAS_MAP_FWD | SAS_MAP_REV, st, flags, ms));
@@ -451,7 +451,7 @@ static int pairs_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint
     HIP_TRY(hipMemsetAsync(meta.p, 0, 16, st));
     if (s.P) {
         const uint64_t tiles = (s.P + MAP_T - 1) / MAP_T;
-        const dim3 tgrid((unsigned)std::min<uint64_t>(tiles, (uint64_t)x->num_cus * MAP_BPC));
+        const dim3 tgrid((unsigned)tile_grid(std::min<uint64_t>(tiles, (uint64_t)x->num_cus * MAP_BPC)));
         TRY(toff.alloc(pool, (tiles + 1) * 8, st));
         TRY(lmin.alloc(pool, s.P * 8, st));
         TRY(lkey.alloc(pool, s.P * 8, st));

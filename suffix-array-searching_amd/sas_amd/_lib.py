@@ -194,6 +194,8 @@ def lib():
     L.sas_locate_edit_verify_ms.restype = C.c_double
     L.sas_locate_edit_dedup_ms.argtypes = [vp]
     L.sas_locate_edit_dedup_ms.restype = C.c_double
+    L.sas_tile_grid_cap.argtypes = []
+    L.sas_tile_grid_cap.restype = u32
     L.sas_align_edit.argtypes = [vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, u32]
     L.sas_align_edit_fixed.argtypes = [vp, vp, u32, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, u32]
     L.sas_revcomp.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32]

@@ -34,6 +34,8 @@ def test_symbols_declared_exported_and_bound():
         assert list(getattr(L, name).argtypes) == sig, name
     assert "sas_locate_edit_verify_ms" in declared and hasattr(raw, "sas_locate_edit_verify_ms")
     assert L.sas_locate_edit_verify_ms.restype == C.c_double
+    assert "sas_tile_grid_cap" in declared and hasattr(raw, "sas_tile_grid_cap")
+    assert L.sas_tile_grid_cap.restype == U32 and list(L.sas_tile_grid_cap.argtypes) == []
     assert (_lib.SAS_ED_TRUNCATED, _lib.SAS_ED_SHORT, _lib.SAS_ED_LONG) == (1, 2, 4) == (TRUNCATED, SHORT, LONG)
     # the header's parameter lists, type by type, and its flag values
     src = open(os.path.join(REPO, "include", "sas.h")).read()
