@@ -624,9 +624,9 @@ double sas_locate_edit_verify_ms(uint64_t* candidates);
 double sas_locate_edit_dedup_ms(uint64_t* proposals);
 /* Debug helper for tests: SAS_TILE_GRID=g in the environment (read at every call) caps at g
  * workgroups the grids of the tiled kernels of sas_locate*, sas_locate_mismatch*,
- * sas_locate_edit*, sas_align_edit*, sas_map_edit*, sas_map_pairs* and sas_revcomp*, so a small
- * batch takes the tile loops of a large one; results do not depend on it.  It only lowers a
- * grid.  This returns the cap in force, 0 for none (unset, empty or not positive). */
+ * sas_locate_edit*, sas_align_edit*, sas_map_edit*, sas_map_pairs*, sas_map_pairs_rescue* and
+ * sas_revcomp*, so a small batch takes the tile loops of a large one; results do not depend on
+ * it.  It only lowers a grid.  This returns the cap in force, 0 for none (unset, empty or not positive). */
 uint32_t sas_tile_grid_cap(void);
 
 /* Where an approximate match starts and its edit script, for ends that sas_locate_edit*
@@ -792,8 +792,8 @@ int sas_map_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m
  * when the bits of 4 np - 1 and of n together exceed the 64-bit sort key.  np == 0 writes
  * nothing.  out_end and out_dist are required, every other output may be NULL.  Flags:
  * SAS_DEVICE_PTRS, SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE.  Other orientations (FF,
- * RF), the rescue of a mate that has no end within k, a mapping quality and SAM text are not
- * part of the call.
+ * RF), the rescue of a mate that has no end within k (sas_map_pairs_rescue below), a mapping quality
+ * and SAM text are not part of the call.
  * With SAS_DEVICE_PTRS the call synchronises on `stream` where sas_map_edit on the same reads
  * does, and nowhere else: the loci scratch and the join's grids are sized from the number of
  * proposed ends, which the host holds already, and the number of loci stays on the device.  With
@@ -813,6 +813,79 @@ int sas_map_pairs_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t 
                         uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
                         uint8_t* out_pflags, uint32_t* out_npairs, uint32_t* out_nbestpairs, void* stream,
                         uint32_t flags);
+
+/* Paired-end mapping with mate rescue: sas_map_pairs, and for a pair that it leaves without a
+ * proper candidate a direct scan, with no seeds, of the window in which the fragment length puts
+ * the other mate.  A mate loses its loci when its seeds are skipped by max_seed_hits (it lies in a
+ * repeat) or when it carries more than k edits; its partner usually maps, and says where to look.
+ * The arguments are sas_map_pairs' with k_rescue behind k, max_anchors behind max_frag and
+ * out_nrescue (per pair, may be NULL) behind out_nbestpairs.  Everything below is a pure function
+ * of D of sas_locate_edit's text (the full-text Sellers D(e) of a query) and of sas_map_pairs'
+ * own definitions for the same k, max_seed_hits, min_frag and max_frag.
+ *   - bounds: k <= k_rescue <= 15 (EINVAL otherwise, checked with the window, before the index);
+ *     every other argument check, index requirement and error is sas_map_pairs';
+ *   - alignments: out_start, out_nruns and out_runs of every read are sas_align_edit's for
+ *     (q_strand, end, k_rescue), with a run stride of 2 k_rescue + 1.  For an end with D(e) <= k
+ *     that is the start and the script it gives with k: the larger bound only adds smaller
+ *     starts to the window w0 .. e, the reported start is the largest that reaches the distance,
+ *     and R does not depend on the window;
+ *   - eligible: pair i is eligible iff its n_pairs under sas_map_pairs is 0, max_anchors > 0 and
+ *     1 <= A(i) <= max_anchors, A(i) the number of loci of reads 2i and 2i + 1 over both strands
+ *     (the unclamped 64-bit sum of their two n_loci).  A pair with n_pairs = 0, max_anchors > 0
+ *     and A(i) > max_anchors gets SAS_PAIR_RESCUE_SKIPPED.  max_anchors = 0 switches rescue off:
+ *     with k_rescue = k the outputs are then byte for byte sas_map_pairs', and out_nrescue is 0;
+ *   - anchors: every locus of an eligible pair is an anchor: a locus of (a, s) with the
+ *     representative (D_a, e_a); b is the other read of the pair, m_b its length.  An anchor is
+ *     skipped when m_b <= k_rescue or m_b > SAS_ED_MAX_M.  The partner is searched on strand 1 - s,
+ *     with q_b when s = 1 and with rc(q_b) when s = 0, by the D of that query: no seeds, no
+ *     max_seed_hits.
+ *       s = 0 (the anchor is the forward mate, f = a and v = b): the window is W = [e_a - m_a +
+ *         min_frag, e_a - m_a + max_frag] cut to [0, n]; the candidates are the e_y in W with
+ *         D(e_y) <= k_rescue; e_x = e_a and D_x = D_a;
+ *       s = 1 (the anchor is the reverse mate, v = a and f = b): W = [e_a + m_b - max_frag,
+ *         e_a + m_b - min_frag] cut to [0, n]; the candidates are the e_x in W with D(e_x) <=
+ *         k_rescue; e_y = e_a and D_y = D_a.
+ *     In both cases F = e_y - e_x + m_f lies in [min_frag, max_frag] and o = f - 2i, as in
+ *     sas_map_pairs;
+ *   - the best candidate is the least (D_x + D_y, o, e_x, e_y) over all anchors.  A candidate of a
+ *     forward anchor and one of a reverse anchor never coincide in (o, e_x, e_y): both ends would
+ *     be locus representatives with F in the window, and the pair would be proper.  So the 64-bit
+ *     key of the join orders the candidates of both sides as it is;
+ *   - out_nrescue[i]: the sum over the pair's anchors of the number of maximal intervals of
+ *     consecutive candidate ends inside that anchor's window, accumulated in 64 bits and clamped
+ *     at UINT32_MAX; 0 for every pair that is not eligible;
+ *   - a pair with at least one candidate is rescued: SAS_PAIR_RESCUED in out_pflags; the anchor
+ *     read gets end = e_a, dist = D_a, strand = s; the other read gets the candidate's end, its D
+ *     (which may exceed k), strand 1 - s and SAS_MAP_RESCUED in out_qflags; both are re-aligned
+ *     as stated above;
+ *   - SAS_PAIR_PROPER, out_npairs, out_nbestpairs, out_nbest, out_nloci, the other out_qflags
+ *     bits and every record of a pair that is proper or not rescued stay what sas_map_pairs
+ *     defines.
+ * One work item of the scan takes SAS_RESCUE_CHUNK consecutive ends of one anchor's window (and
+ * the m_b + k_rescue + 1 columns before them), so a window of spread + 1 ends is ceil((spread + 1)
+ * / SAS_RESCUE_CHUNK) items.  With SAS_DEVICE_PTRS the call synchronises exactly where
+ * sas_map_pairs does: the anchor count stays on the device, the scratch is sized from the number
+ * of proposed ends and the scan's grid is capped and strides over the count.  With host pointers:
+ * synchronous, bytes always validated. */
+#define SAS_PAIR_RESCUED        2u /* out_pflags: placed by a window scan from an anchor            */
+#define SAS_PAIR_RESCUE_SKIPPED 4u /* out_pflags: no proper candidate, more than max_anchors loci  */
+#define SAS_MAP_RESCUED         8u /* out_qflags: this read's end comes from the window scan        */
+#define SAS_RESCUE_CHUNK 128u      /* window ends per work item of the scan                         */
+int sas_map_pairs_rescue(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
+                         uint64_t npairs, uint32_t k, uint32_t k_rescue, uint64_t max_seed_hits,
+                         uint32_t min_frag, uint32_t max_frag, uint64_t max_anchors, void* out_end,
+                         void* out_start, uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest,
+                         uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
+                         uint8_t* out_pflags, uint32_t* out_npairs, uint32_t* out_nbestpairs,
+                         uint32_t* out_nrescue, void* stream, uint32_t flags);
+/* sas_map_pairs_rescue for fixed-length reads qbytes[k*m .. (k+1)*m). */
+int sas_map_pairs_rescue_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t npairs,
+                               uint32_t k, uint32_t k_rescue, uint64_t max_seed_hits, uint32_t min_frag,
+                               uint32_t max_frag, uint64_t max_anchors, void* out_end, void* out_start,
+                               uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest, uint32_t* out_nloci,
+                               uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags, uint8_t* out_pflags,
+                               uint32_t* out_npairs, uint32_t* out_nbestpairs, uint32_t* out_nrescue,
+                               void* stream, uint32_t flags);
 
 /* Timing helper for benches: run `reps` back-to-back fixed-length searches on
  * device buffers and report the average duration of the search kernel itself

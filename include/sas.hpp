@@ -467,6 +467,53 @@ class SaNaive {
         return r;
     }
 
+    /* Result of map_pairs_rescue: MappedPairs' fields (pflags also SAS_PAIR_RESCUED and
+     * SAS_PAIR_RESCUE_SKIPPED, qflags also SAS_MAP_RESCUED, stride = 2 k_rescue + 1) and per pair
+     * n_rescue = the runs of candidate ends in its anchors' windows */
+    struct MappedPairsRescue : MappedPairs {
+        std::vector<uint32_t> n_rescue;
+    };
+
+    /* map_pairs with mate rescue (sas_map_pairs_rescue): a pair without a proper placement and with
+     * at most max_anchors loci (0: no rescue) has the fragment window of each locus scanned for the
+     * other mate within k_rescue >= k edits, with no seeds */
+    MappedPairsRescue map_pairs_rescue(const std::vector<Seq>& qs, uint32_t k, uint32_t k_rescue, uint32_t min_frag,
+                                       uint32_t max_frag, uint64_t max_anchors, uint64_t max_seed_hits = 0,
+                                       uint32_t flags = 0) const {
+        if (qs.size() % 2) throw std::invalid_argument("map_pairs_rescue: an odd number of reads");
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        MappedPairsRescue r;
+        const size_t nq = qs.size(), np = nq / 2;
+        r.stride = 2 * (size_t)k_rescue + 1;
+        r.end.assign(nq, n_);
+        r.start.assign(nq, n_);
+        r.dist.assign(nq, (uint8_t)SAS_AL_NONE_DIST);
+        r.strand.assign(nq, 0);
+        r.nruns.assign(nq, 0);
+        r.qflags.assign(nq, 0);
+        r.n_best.assign(nq, 0);
+        r.n_loci.assign(nq, 0);
+        r.runs.assign(nq * r.stride, 0);
+        r.pflags.assign(np, 0);
+        r.n_pairs.assign(np, 0);
+        r.n_best_pairs.assign(np, 0);
+        r.n_rescue.assign(np, 0);
+        check(sas_map_pairs_rescue(h_, bytes.data(), qoff.data(), len.data(), np, k, k_rescue, max_seed_hits, min_frag,
+                                   max_frag, max_anchors, r.end.data(), r.start.data(), r.dist.data(),
+                                   r.strand.data(), r.n_best.data(), r.n_loci.data(), r.nruns.data(), r.runs.data(),
+                                   r.qflags.data(), r.pflags.data(), r.n_pairs.data(), r.n_best_pairs.data(),
+                                   r.n_rescue.data(), nullptr, flags));
+        return r;
+    }
+
     /* Search::search_range over a Range<&Seq> (sas/util.rs:41-46, unimplemented!() upstream):
      * the positions of the suffixes s with a <= s < b, in SA order.  One range on host
      * pointers: two lower bounds and one sas_copy_sa64; batches of ranges are

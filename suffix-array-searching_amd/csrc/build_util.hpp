@@ -14,7 +14,7 @@ static inline unsigned grid_for(uint64_t count, unsigned block = 256) {
 
 // debug: SAS_TILE_GRID=g caps at g workgroups the grid of every output-centric tiled kernel
 // (k_locate_fill, k_mm_verify, k_ed_verify, k_al_align, k_map_fill, k_map_select, k_pair_heads,
-// k_pair_loci, k_pair_join) and of the grid(count) helpers of their calls, so a small batch takes
+// k_pair_loci, k_pair_join, k_pair_rescue) and of the grid(count) helpers of their calls, so a small batch takes
 // the tile loop that a large one needs: g = 1 hands every tile to one workgroup in turn
 // (tests/test_gpu_tiles.py).  Read at every call; it only ever lowers a grid: unset, empty or
 // non-positive is no cap.  sas_tile_grid_cap (sas.h) returns the cap in force, 0 for none

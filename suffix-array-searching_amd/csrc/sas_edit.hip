@@ -85,27 +85,6 @@ struct EdArgs {
     ulonglong2* dists;      // per candidate: the distance of bit i in bits [4 i, 4 i + 4)
 };
 
-// even bits of x (bit 2 p -> bit p)
-__device__ __forceinline__ uint32_t ed_even_bits(uint64_t x) {
-    x &= 0x5555555555555555ull;
-    x = (x | (x >> 1)) & 0x3333333333333333ull;
-    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
-    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
-    return (uint32_t)x;
-}
-
-// The bit planes of query chars [32 j, 32 j + 32): bit r of lo / hi = the low / high bit of char
-// 32 j + r (pack_query_word has char r in bits 63 - 2 r, 62 - 2 r; zero behind m)
-__device__ __forceinline__ void ed_planes32(const uint8_t* __restrict__ qb, uint32_t m, uint32_t j, uint32_t* lo,
-                                            uint32_t* hi) {
-    uint32_t bad = 0;
-    const uint64_t w = pack_query_word(qb, m, j, &bad);
-    *lo = __brev(ed_even_bits(w));
-    *hi = __brev(ed_even_bits(w >> 1));
-}
-
 // Candidate = an occurrence of piece i at text position pv.  NW words of 64 rows (m <= 64 NW)
 template <int NW>
 __device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64_t s0,
@@ -117,43 +96,14 @@ __device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64
     const int64_t e0 = s0 + (int64_t)m - k;                         // the end of bit 0
     uint32_t mask = 0;
     uint64_t d0 = 0, d1 = 0;
-    uint64_t L[NW], H[NW], V[NW], Pv[NW], Mv[NW];
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-        uint32_t l0, h0, l1, h1;
-        ed_planes32(qb, m, 2 * w, &l0, &h0);
-        ed_planes32(qb, m, 2 * w + 1, &l1, &h1);
-        L[w] = ((uint64_t)l1 << 32) | l0;
-        H[w] = ((uint64_t)h1 << 32) | h0;
-        const uint32_t rows = m > 64u * w ? m - 64u * w : 0u;       // rows of the query in this word
-        V[w] = rows >= 64 ? ~0ull : ((1ull << rows) - 1ull);
-        Pv[w] = ~0ull;
-        Mv[w] = 0;
-    }
-    const uint32_t lw = (m - 1) >> 6, lb = (m - 1) & 63;            // row m - 1: word and bit
+    EdMyers<NW> my;
+    my.init(qb, m);
     int64_t score = m;
     for (int64_t col = w0; col < w1; col += 32) {
         uint64_t tx = text_chars32(a.tw, (uint64_t)col);            // col < w1 <= n
         const int64_t cend = col + 32 < w1 ? col + 32 : w1;
         for (int64_t c = col; c < cend; c++, tx <<= 2) {
-            const uint64_t cl = 0ull - ((tx >> 62) & 1ull), ch = 0ull - (tx >> 63);
-            int hin = 0;                                            // free start: 0 into row 0
-#pragma unroll
-            for (int w = 0; w < NW; w++) {
-                uint64_t Eq = ~(L[w] ^ cl) & ~(H[w] ^ ch) & V[w];
-                const uint64_t Xv = Eq | Mv[w];
-                Eq |= hin < 0 ? 1ull : 0ull;
-                const uint64_t Xh = (((Eq & Pv[w]) + Pv[w]) ^ Pv[w]) | Eq;
-                uint64_t Ph = Mv[w] | ~(Xh | Pv[w]);
-                uint64_t Mh = Pv[w] & Xh;
-                if ((uint32_t)w == lw) score += (int64_t)((Ph >> lb) & 1ull) - (int64_t)((Mh >> lb) & 1ull);
-                const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
-                Ph = (Ph << 1) | (hin > 0 ? 1ull : 0ull);
-                Mh = (Mh << 1) | (hin < 0 ? 1ull : 0ull);
-                Pv[w] = Mh | ~(Xv | Ph);
-                Mv[w] = Ph & Xv;
-                hin = hout;
-            }
+            score += my.column(tx);
             const int64_t e = c + 1;                                // the score is D of end c + 1
             if (score <= k && e >= e0) {
                 const uint32_t i = (uint32_t)(e - e0);              // <= 2k: e <= w1 <= s0 + m + k

@@ -44,6 +44,10 @@ SAS_MAP_FWD = 1  # sas_map_edit's strands mask
 SAS_MAP_REV = 2
 SAS_PAIR_PROPER = 1  # sas_map_pairs' per-pair flags
 SAS_PAIR_MAX_SPREAD = 65535  # the largest max_frag - min_frag
+SAS_PAIR_RESCUED = 2  # sas_map_pairs_rescue's per-pair flags
+SAS_PAIR_RESCUE_SKIPPED = 4
+SAS_MAP_RESCUED = 8  # its per-read flag, beside the SAS_ED_* bits of out_qflags
+SAS_RESCUE_CHUNK = 128  # window ends per work item of its scan
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
 SAS_BUILD_SA40 = 1 << 8
@@ -204,6 +208,8 @@ def lib():
     L.sas_map_edit_fixed.argtypes = [vp, vp, u32, u64, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32]
     L.sas_map_pairs.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u32] + [vp] * 13 + [u32]
     L.sas_map_pairs_fixed.argtypes = [vp, vp, u32, u64, u32, u64, u32, u32] + [vp] * 13 + [u32]
+    L.sas_map_pairs_rescue.argtypes = [vp, vp, vp, vp, u64, u32, u32, u64, u32, u32, u64] + [vp] * 14 + [u32]
+    L.sas_map_pairs_rescue_fixed.argtypes = [vp, vp, u32, u64, u32, u32, u64, u32, u32, u64] + [vp] * 14 + [u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]

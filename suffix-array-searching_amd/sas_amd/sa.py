@@ -33,6 +33,8 @@ class Counter:
 Mapped = namedtuple("Mapped", "end start dist strand n_best n_loci nruns runs qflags")
 # SaNaive.map_pairs (sas_map_pairs): Mapped's fields per read, then three per pair
 MappedPairs = namedtuple("MappedPairs", Mapped._fields + ("pflags", "n_pairs", "n_best_pairs"))
+# SaNaive.map_pairs_rescue (sas_map_pairs_rescue): MappedPairs' fields, then one more per pair
+MappedPairsRescue = namedtuple("MappedPairsRescue", MappedPairs._fields + ("n_rescue",))
 
 
 def _is_cuda(x) -> bool:
@@ -954,18 +956,27 @@ class SaNaive:
         return self._map_edit(qbytes, None, None, int(m), nq, k, max_seed_hits, strands, u32, stream, flags)
 
     # -- paired-end mapping: the mates of a pair placed together (sas_map_pairs*)
-    def _map_pairs(self, qbytes, qoff, qlen, m, nq, k, min_frag, max_frag, max_seed_hits, u32, stream, flags):
+    def _map_pairs(self, qbytes, qoff, qlen, m, nq, k, min_frag, max_frag, max_seed_hits, u32, stream, flags,
+                   rescue=None):
+        """rescue: None (sas_map_pairs*) or (k_rescue, max_anchors) (sas_map_pairs_rescue*)."""
         if nq % 2:
             raise ValueError(f"paired reads come interleaved, mate 1 then mate 2: {nq} reads is an odd number")
         L = lib()
         k = int(k)
-        np_, stride = nq // 2, 2 * k + 1
+        np_, stride = nq // 2, 2 * (k if rescue is None else int(rescue[0])) + 1
+        Rec = MappedPairs if rescue is None else MappedPairsRescue
 
         def call(r, st, fl):
-            tail = (k, int(max_seed_hits), int(min_frag), int(max_frag)) + tuple(_ptr(v) for v in r) + (st, fl)
+            ptrs = tuple(_ptr(v) for v in r) + (st, fl)
+            if rescue is None:
+                tail = (k, int(max_seed_hits), int(min_frag), int(max_frag)) + ptrs
+                ragged, fixed = L.sas_map_pairs, L.sas_map_pairs_fixed
+            else:
+                tail = (k, int(rescue[0]), int(max_seed_hits), int(min_frag), int(max_frag), int(rescue[1])) + ptrs
+                ragged, fixed = L.sas_map_pairs_rescue, L.sas_map_pairs_rescue_fixed
             if qoff is not None:
-                return L.sas_map_pairs(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), np_, *tail)
-            return L.sas_map_pairs_fixed(self._h, _ptr(qbytes), m, np_, *tail)
+                return ragged(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), np_, *tail)
+            return fixed(self._h, _ptr(qbytes), m, np_, *tail)
 
         if _is_cuda(qbytes):
             import torch
@@ -976,18 +987,20 @@ class SaNaive:
 
             def new(shape, dtype):
                 return torch.empty(shape, dtype=dtype, device=d)
-            r = MappedPairs(new(nq, dt), new(nq, dt), new(nq, torch.uint8), new(nq, torch.uint8),
-                            new(nq, torch.int32), new(nq, torch.int32), new(nq, torch.uint8),
-                            new((nq, stride), torch.int16), new(nq, torch.uint8), new(np_, torch.uint8),
-                            new(np_, torch.int32), new(np_, torch.int32))
+            r = Rec(new(nq, dt), new(nq, dt), new(nq, torch.uint8), new(nq, torch.uint8),
+                    new(nq, torch.int32), new(nq, torch.int32), new(nq, torch.uint8),
+                    new((nq, stride), torch.int16), new(nq, torch.uint8), new(np_, torch.uint8),
+                    new(np_, torch.int32), new(np_, torch.int32),
+                    *([] if rescue is None else [new(np_, torch.int32)]))
             check(call(r, st, fl))
             return r
         qbytes = _as_u8(qbytes)
         pt = np.uint32 if u32 else np.uint64
-        r = MappedPairs(np.empty(nq, pt), np.empty(nq, pt), np.empty(nq, np.uint8), np.empty(nq, np.uint8),
-                        np.empty(nq, np.uint32), np.empty(nq, np.uint32), np.empty(nq, np.uint8),
-                        np.empty((nq, stride), np.uint16), np.empty(nq, np.uint8), np.empty(np_, np.uint8),
-                        np.empty(np_, np.uint32), np.empty(np_, np.uint32))
+        r = Rec(np.empty(nq, pt), np.empty(nq, pt), np.empty(nq, np.uint8), np.empty(nq, np.uint8),
+                np.empty(nq, np.uint32), np.empty(nq, np.uint32), np.empty(nq, np.uint8),
+                np.empty((nq, stride), np.uint16), np.empty(nq, np.uint8), np.empty(np_, np.uint8),
+                np.empty(np_, np.uint32), np.empty(np_, np.uint32),
+                *([] if rescue is None else [np.empty(np_, np.uint32)]))
         check(call(r, stream, flags | (_lib.SAS_LOCATE_U32 if u32 else 0)))
         return r
 
@@ -1021,6 +1034,36 @@ class SaNaive:
         nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
         return self._map_pairs(qbytes, None, None, int(m), nq, k, min_frag, max_frag, max_seed_hits, u32, stream,
                                flags)
+
+    # -- paired-end mapping with mate rescue (sas_map_pairs_rescue*)
+    def map_pairs_rescue(self, qbytes, qoff, qlen, k: int, k_rescue: int, min_frag: int, max_frag: int,
+                         max_anchors: int, max_seed_hits: int = 0, u32: bool = False, flags: int = 0, stream=None):
+        """map_pairs with mate rescue (sas_map_pairs_rescue).  A pair without a proper candidate and
+        with 1 .. max_anchors loci over both mates and strands (max_anchors = 0: no rescue) has the
+        fragment window of every locus scanned, with no seeds, for the other mate on the opposite
+        strand within k_rescue >= k edits.  Returns the named tuple MappedPairsRescue: MappedPairs'
+        fields and n_rescue, per pair the runs of candidate ends in its anchors' windows.  A rescued
+        pair has SAS_PAIR_RESCUED in pflags, the anchor read its locus, the other read the best
+        candidate's end, its distance (which may exceed k) and SAS_MAP_RESCUED in qflags; a pair
+        with more than max_anchors loci has SAS_PAIR_RESCUE_SKIPPED.  runs has 2 k_rescue + 1 slots
+        per read; everything else is map_pairs'."""
+        dev = _is_cuda(qbytes)
+        if not dev:
+            qoff = np.ascontiguousarray(qoff, np.uint64)
+            qlen = np.ascontiguousarray(qlen, np.uint32)
+        nq = int(qoff.numel() if dev else len(qoff))
+        return self._map_pairs(qbytes, qoff, qlen, 0, nq, k, min_frag, max_frag, max_seed_hits, u32, stream, flags,
+                               rescue=(k_rescue, max_anchors))
+
+    def map_pairs_rescue_fixed(self, qbytes, m: int, k: int, k_rescue: int, min_frag: int, max_frag: int,
+                               max_anchors: int, max_seed_hits: int = 0, u32: bool = False, flags: int = 0,
+                               stream=None):
+        """map_pairs_rescue for fixed-length reads qbytes[i*m : (i+1)*m] (sas_map_pairs_rescue_fixed)."""
+        if m <= 0:
+            raise ValueError("use map_pairs_rescue for empty reads")
+        nq = (qbytes.numel() if _is_cuda(qbytes) else len(qbytes)) // m
+        return self._map_pairs(qbytes, None, None, int(m), nq, k, min_frag, max_frag, max_seed_hits, u32, stream,
+                               flags, rescue=(k_rescue, max_anchors))
 
     def time_fixed(self, d_qbytes, m: int, nq: int, d_out, algo="plain", reps=1, stream=None, flags=0):
         """Average (kernel_ns, call_ns) of `reps` back-to-back searches on device buffers."""
