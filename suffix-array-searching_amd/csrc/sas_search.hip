@@ -29,6 +29,7 @@
 // Text compares are 2-bit packed: 32 chars per u64 compare.
 #include "common.hpp"
 #include "host_stage.hpp"
+#include "qllcp_bisect.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -1619,23 +1620,20 @@ __global__ __launch_bounds__(QLLCP_BLOCK(QW), QLLCP_BLOCK(QW) * 2 / 256) void k_
         if (!done) {
             using rk_t = typename std::conditional<R32, uint32_t, uint64_t>::type;
             const rk_t sa_n = (rk_t)a.sa_n;
+            // no wrap in 32 bits: this query passed 4 kq + C64 < sa_n above, so kb, s0 <= kb + C64
+            // and L0 <= kb + C64 + 1 are at most sa_n; U is formed in 64 bits (qllcp_bisect.hpp)
             const rk_t kb = 4 * (rk_t)kq;
             const rk_t s0 = kb + QL_C16(st);
             const rk_t L0 = kb + QL_C64(st) + ((st & QL_LAM0) ? 1 : 0);
-            rk_t U = (st & QL_END) ? sa_n : 4 * (rk_t)kU + QL_FU(st);
-            if (U >= sa_n) U = sa_n;
+            const rk_t U = qllcp_right_bound<rk_t>(kU, QL_FU(st), (st & QL_END) != 0, a.sa_n);
             const uint32_t kappa = (st & QL_X32) ? 32u : 16u;
             rk_t l = 0, r = sa_n;
             uint64_t pr = QUAD_NO_SA;
             uint32_t llcp = 0, rlcp = 0;
             for (;;) {
                 rk_t mid = 0;
-                while (l < r) {  // ALU only, as stree_tail
-                    mid = (l + r) >> 1;
-                    if (mid < L0) l = mid + 1;
-                    else if (mid >= U) r = mid;
-                    else break;
-                }
+                while (l < r)  // ALU only, as stree_tail
+                    if (qllcp_bisect_step<rk_t>(l, r, L0, U, mid)) break;
                 if (!(l < r)) break;
                 const uint4 e = a.llcp[mid];
                 const uint32_t x = (e.y >> 8) & SAS_LLCP_CAP, y = e.y >> 20;

@@ -450,12 +450,50 @@ def test_wide_doubling_rounds(sas, sadef):
         assert idx.stats()["sa_rounds"] > 0
 
 
+def plant_t_blocks(torch, t, n, rng, clear):
+    """64 copies of a 400-char block that starts with 20 'T's, written into the device text t at
+    random multiples of 4096 that leave [clear[0], clear[1]) alone: the copies' first suffixes sort
+    into the text's top few hundred ranks, in runs of 64 equal 32-char keys.  Returns the starts."""
+    blk = torch.from_numpy(np.concatenate([np.full(20, 3, np.uint8), rng.integers(0, 4, 380, dtype=np.uint8)])).cuda()
+    at = np.arange(1 << 20, n - 1000, 4096, dtype=np.int64)
+    at = at[(at + 400 <= clear[0]) | (at >= clear[1])]
+    starts = np.sort(rng.choice(at, 64, replace=False))
+    for s in starts:
+        t[int(s):int(s) + 400] = blk
+    return starts
+
+
+def t_block_queries(ht, starts, rng):
+    """Queries of 33..256 chars from the first 9 offsets of 48 of the planted copies (>= 12 leading
+    'T's: among the text's top ~10^3 suffixes), each also with one char changed past char 32."""
+    qs = []
+    for s in starts[:48]:
+        for m in (33, 48, 64, 100, 200, 256):
+            o = int(s) + int(rng.integers(0, 9))
+            q = ht[o:o + m].copy()
+            qs.append(q)
+            mq = q.copy()
+            k = int(rng.integers(32, m))
+            mq[k] = (mq[k] + 1 + rng.integers(0, 3)) % 4
+            qs.append(mq)
+    return qs
+
+
 def test_large_text_sampled(sas):
     """n > 2^31 (the wide builder path for real): GPU adjacency + permutation
-    check (sas/sa_search.rs:36-38) and sampled positions vs the oracle."""
+    check (sas/sa_search.rs:36-38) and sampled positions vs the oracle.  The planted blocks of
+    test_llcp_tails_beyond_u32 put queries at the top of the SA, at ranks above 2^31, where
+    k_sa_quad_llcp's walk runs with 32-bit ranks (R32: l + r passes 2^32; tests/test_qllcp_host.py
+    checks that step on the CPU).  A copy of the 4099-char `random` text across position 2^31
+    carries the approximate-matching calls there (tests/test_gpu_far.py: check_slice)."""
     import torch
+    from test_far_host import M, SMALL_N, small_text
+    from test_gpu_far import check_slice
     n = (1 << 31) + 12345
     t = sas.random_string(n, seed=123, device="cuda")
+    at = (1 << 31) - 2048
+    starts = plant_t_blocks(torch, t, n, np.random.default_rng(8), (at - M, at + SMALL_N + M))
+    t[at:at + SMALL_N] = torch.from_numpy(small_text()).cuda()
     idx = sas.SaNaive.build(t, lcp=False, stree=True, llcp=True, verify=True)
     ht = t.cpu().numpy()
     del t
@@ -469,6 +507,24 @@ def test_large_text_sampled(sas):
     expect = oracle_positions(ht, sa, qb, np.arange(nq, dtype=np.uint64) * m, np.full(nq, m, np.uint32))
     for algo in ALGOS:
         assert np.array_equal(idx.search_fixed(qb, m, algo=algo), expect), algo
+    # the walk at the SA's top
+    qs = t_block_queries(ht, starts, rng)
+    qs += [np.concatenate([ht[n - k:], np.zeros(j, np.uint8)]) for k in (20, 40, 300) for j in (0, 30)]
+    buf, qo, ql = pack(qs)
+    expect = oracle_positions(ht, sa, buf[:-64], qo, ql)
+    top = sa[1 << 31:]   # the suffixes of the ranks from 2^31 on
+    above = int(np.isin(expect[:48 * 12], top).sum() + (expect[:48 * 12] == n).sum())
+    assert above >= 48 * 12, above  # the planted copies' queries are answered at ranks >= 2^31
+    for algo in ALGOS:
+        got = idx.search_batch(buf, qo, ql, algo=algo)
+        bad = np.nonzero(got != expect)[0]
+        assert len(bad) == 0, (algo, bad[:10])
+    del sa
+    try:   # a failure in there must not keep this index's HBM from the tests that follow
+        counts = check_slice(torch, idx, ht, at, 1 << 31, u32=True)
+    finally:
+        idx.free()
+    print("test_large_text_sampled: ranks >= 2^31:", above, "slice:", counts)
 
 
 def test_ragged_unaligned_device_queries(sas):
@@ -810,30 +866,21 @@ def test_llcp_tails_beyond_u32(sas):
     the absolute quad layout, which it needs), STREE_LLCP and LLCP equal PLAIN, and every PLAIN
     answer is proven the exact lower bound on the host text (sas/sa_search.rs:98-112)."""
     import torch
+    from test_far_host import M, SMALL_N, small_text
+    from test_gpu_far import check_slice
     n = (1 << 32) + 12345
     t = sas.random_string(n, seed=987, device="cuda")
     rng = np.random.default_rng(8)
-    blk = torch.from_numpy(np.concatenate([np.full(20, 3, np.uint8), rng.integers(0, 4, 380, dtype=np.uint8)])).cuda()
-    starts = np.sort(rng.choice(np.arange(1 << 20, n - 1000, 4096, dtype=np.int64), 64, replace=False))
-    for s in starts:
-        t[int(s):int(s) + 400] = blk
+    at = (1 << 32) - 2048   # a copy of the 4099-char `random` text across position 2^32 (check_slice below)
+    starts = plant_t_blocks(torch, t, n, rng, (at - M, at + SMALL_N + M))
+    t[at:at + SMALL_N] = torch.from_numpy(small_text()).cuda()
     ht = t.cpu().numpy()
     idx = sas.SaNaive.build(t, lcp=False, stree=True, sector=False, quad="abs", llcp=True, prefix=False)
     del t
     torch.cuda.empty_cache()
     st = idx.stats()
     assert st["sa_width"] == 5 and st["quad_fan"] == 17 and st["llcp_bytes"] == 16 * n
-    qs = []
-    for s in starts[:48]:
-        for m in (33, 48, 64, 100, 200, 256):
-            # >= 12 leading 'T's: among the text's top ~10^3 suffixes, ranks above 2^32
-            o = int(s) + int(rng.integers(0, 9))
-            q = ht[o:o + m].copy()
-            qs.append(q)
-            mq = q.copy()
-            k = int(rng.integers(32, m))
-            mq[k] = (mq[k] + 1 + rng.integers(0, 3)) % 4
-            qs.append(mq)
+    qs = t_block_queries(ht, starts, rng)   # ranks above 2^32
     hi_offs = rng.integers((1 << 32) - 100, n - 300, 200)
     qs += [ht[o:o + m] for o, m in zip(hi_offs, rng.integers(33, 257, 200))]
     qs += [np.concatenate([ht[n - k:], np.zeros(j, np.uint8)]) for k in (20, 40, 300) for j in (0, 30)]
@@ -857,7 +904,12 @@ def test_llcp_tails_beyond_u32(sas):
             assert bytes(ht[int(pair[0]):int(pair[0]) + len(q)]) < qb, k
         above += r >= (1 << 32)
     assert above >= 48 * 12  # the planted copies' queries were answered at ranks above 2^32
-    idx.free()
+    # approximate matching across position 2^32; SAS_LOCATE_U32 is refused by all six calls
+    try:   # a failure in there must not keep this index's HBM from the tests that follow
+        counts = check_slice(torch, idx, ht, at, 1 << 32, u32=False)
+    finally:
+        idx.free()
+    print("test_llcp_tails_beyond_u32: ranks >= 2^32:", above, "slice:", counts)
 
 
 def test_fasta_genome_like_end_to_end(sas, tmp_path):
