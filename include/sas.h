@@ -44,7 +44,9 @@ typedef struct sas_index sas_index;
 #define SAS_DEVICE_PTRS   (1u << 0)  /* all array arguments are device pointers          */
 #define SAS_BUILD_LCP     (1u << 1)  /* also build the LCP array (Kasai semantics)       */
 #define SAS_BUILD_STREE   (1u << 2)  /* also build the S-tree over 16-char SA keys       */
-#define SAS_BUILD_VERIFY  (1u << 3)  /* run the adjacency + permutation check on the SA  */
+#define SAS_BUILD_VERIFY  (1u << 3)  /* run the range + adjacency + permutation check on
+                                        the whole SA, a caller's at its own width: see
+                                        sas_verify                                        */
 #define SAS_NO_LDS_TOP    (1u << 4)  /* search: do not serve the top levels from LDS     */
 #define SAS_VALIDATE      (1u << 5)  /* search: reject query bytes > 3 (synchronises)    */
 #define SAS_ROUTE_PACKED  (1u << 26)  /* sas_route_pack(_cap): write each query as one 2-bit
@@ -398,9 +400,24 @@ int sas_search_packed(const sas_index* index, const uint64_t* qwords, uint32_t m
 int sas_extract(const sas_index* index, const uint64_t* pos, const uint32_t* len, const uint64_t* out_off,
                 uint64_t count, uint8_t* out, void* stream, uint32_t flags);
 
-/* GPU check of the SA: strictly increasing adjacent suffixes (the
- * reference's build assertion, sas/sa_search.rs:36-38) + permutation.
- * Returns 0 if valid, EINVAL (with message) if not. */
+/* GPU check of the SA (SAS_BUILD_VERIFY at build, sas_verify on a built index).  In this order,
+ * each EINVAL with its message:
+ *   1. every entry is < n                        "suffix array holds an entry >= n"
+ *   2. the suffixes of adjacent ranks strictly increase, whole suffixes compared, a proper
+ *      prefix before the longer one (the reference's build assertion, sas/sa_search.rs:36-38)
+ *                                                "suffix array not sorted: ..."
+ *   3. (whole indexes) every position occurs     "suffix array is not a permutation of 0..n"
+ * n strictly increasing suffixes with starts < n are pairwise distinct, hence a permutation:
+ * once 1 and 2 pass on a whole index, 3 cannot fail, and no caller should wait for its message.
+ * SAS_BUILD_VERIFY checks the whole array, a shard's too (sas_build_shard: all n entries of
+ * the caller's array, before the rank range is cut out), and a caller's array at the caller's
+ * own width: a u64 or packed 40-bit entry >= n fails check 1 even where the index's narrower
+ * entry would drop its high bits.  Without the flag nothing about a caller's array is promised:
+ * an entry >= n then makes the build read outside the text.
+ * sas_verify checks what the index holds: a shard's held ranks only (checks 1 and 2 on
+ * [rank_lo, rank_lo + sa_entries), not the pair across either edge), so a fault of the caller's
+ * array outside them goes unseen.  ENOTSUP for a bucket-line index (SAS_BUILD_TAG_LINES holds
+ * no SA array: verify at build).  Returns 0 if valid. */
 int sas_verify(const sas_index* index);
 
 /* Ragged batch: query k = qbytes[qoff[k] .. qoff[k] + qlen[k]).

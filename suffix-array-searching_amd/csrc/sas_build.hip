@@ -1558,31 +1558,49 @@ static int copy_in_sa(const void* src, uint8_t* dst, uint64_t bytes, bool dev) {
     return 0;
 }
 
-// Caller's SA (host or device, 4 / 5 / 8 bytes per entry) -> this index's width.
+// Caller's SA (host or device, 4 / 5 / 8 bytes per entry) -> this index's width.  A narrowing
+// store drops the high bits, so the range check is made here, on the caller's own value
+// (bad, if given: bit 0 for an entry >= n); verify_sa only ever sees the stored one.
 template <int WI, int WO>
-__global__ void k_convert_sa(const uint8_t* __restrict__ in, uint64_t n, uint8_t* __restrict__ out) {
+__global__ void k_convert_sa(const uint8_t* __restrict__ in, uint64_t n, uint8_t* __restrict__ out,
+                             uint32_t* __restrict__ bad) {
     GRID_STRIDE(i, n) {
         uint64_t v;
         if (WI == 8) v = reinterpret_cast<const uint64_t*>(in)[i];
         else v = SaView<WI>{in}[i];
+        if (bad && v >= n) atomicOr(bad, 1u);
         sa_put<WO>(out, i, v);
     }
 }
 
-static int load_sa(const void* src, uint64_t n, int wi, bool dev, uint8_t* dst, uint32_t wo) {
+// check (SAS_BUILD_VERIFY): fail on an entry >= n at the caller's width.  Equal widths are a
+// plain copy: verify_sa reads every bit of those.
+static int load_sa(const void* src, uint64_t n, int wi, bool dev, uint8_t* dst, uint32_t wo, bool check) {
     const uint64_t bytes = n * (uint64_t)wi;
     if ((uint32_t)wi == wo)
         return copy_in_sa(src, dst, bytes, dev);
-    DevBuf staged;
+    DevBuf staged, bad;
     TRY(staged.alloc(bytes + 8, "caller SA staging"));
     TRY(copy_in_sa(src, staged.as<uint8_t>(), bytes, dev));
+    uint32_t* flag = nullptr;
+    if (check) {
+        TRY(bad.alloc(4, "caller SA range flag"));
+        HIP_TRY(hipMemset(bad.p, 0, 4));
+        flag = bad.as<uint32_t>();
+    }
     const uint8_t* in = staged.as<uint8_t>();
-    if (wi == 4 && wo == 5) hipLaunchKernelGGL((k_convert_sa<4, 5>), dim3(grid_for(n)), dim3(256), 0, 0, in, n, dst);
-    else if (wi == 5 && wo == 4) hipLaunchKernelGGL((k_convert_sa<5, 4>), dim3(grid_for(n)), dim3(256), 0, 0, in, n, dst);
-    else if (wi == 8 && wo == 4) hipLaunchKernelGGL((k_convert_sa<8, 4>), dim3(grid_for(n)), dim3(256), 0, 0, in, n, dst);
-    else hipLaunchKernelGGL((k_convert_sa<8, 5>), dim3(grid_for(n)), dim3(256), 0, 0, in, n, dst);
+    const dim3 g(grid_for(n)), b(256);
+    if (wi == 4 && wo == 5) hipLaunchKernelGGL((k_convert_sa<4, 5>), g, b, 0, 0, in, n, dst, flag);
+    else if (wi == 5 && wo == 4) hipLaunchKernelGGL((k_convert_sa<5, 4>), g, b, 0, 0, in, n, dst, flag);
+    else if (wi == 8 && wo == 4) hipLaunchKernelGGL((k_convert_sa<8, 4>), g, b, 0, 0, in, n, dst, flag);
+    else hipLaunchKernelGGL((k_convert_sa<8, 5>), g, b, 0, 0, in, n, dst, flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    if (check) {
+        uint32_t h = 0;
+        HIP_TRY(hipMemcpy(&h, bad.p, 4, hipMemcpyDeviceToHost));
+        if (h & 1) SAS_FAIL(EINVAL, "suffix array holds an entry >= n");
+    }
     return 0;
 }
 
@@ -1672,7 +1690,7 @@ static int build_impl(const uint8_t* text, uint64_t n, const void* sa_or_null, i
     const uint64_t sa_bytes_full = n * W + (W == 5 ? SAS_SA40_PAD : 16);
     TRY(sa.alloc(sa_bytes_full, "suffix array"));
     if (sa_or_null) {
-        TRY(load_sa(sa_or_null, n, sa_width, dev, sa.as<uint8_t>(), W));
+        TRY(load_sa(sa_or_null, n, sa_width, dev, sa.as<uint8_t>(), W, (flags & SAS_BUILD_VERIFY) != 0));
     } else {
         uint64_t s0 = now_ns();
         if (W == 5) {
