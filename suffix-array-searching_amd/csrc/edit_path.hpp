@@ -6,8 +6,8 @@
 // Steps 1..6 of sas_edit.hip up to the offsets; the scratch that the calls behind them read
 // stays in the state
 struct EdState {
-    hipMemPool_t pool = nullptr;
-    MmPoolBuf poff, plen, lohi, coff, qfl, mask, kbase, dists, pscan, keys, vals, uscan;
+    SeedState seed;
+    MmPoolBuf mask, kbase, dists, pscan, keys, vals, uscan;
     const uint64_t* skeys = nullptr;  // the P sorted proposals, key = (query << ebits) | end;
     const uint8_t* svals = nullptr;   // their distances (equal keys carry equal distances)
     uint64_t C = 0, P = 0;            // P == 0: nothing was proposed, skeys / svals are null

@@ -2,7 +2,9 @@
 // fragment-length join; sas_rescue.hip: sas_map_pairs_rescue, the join and a window scan for the
 // mate that has no locus): steps 1..3 below (pair_join_batch), the records and the alignments
 // (steps 4 and 5, pair_finish) and the argument checks and host-pointer path of both calls
-// (pairs_impl).  Pair i is reads 2i and 2i + 1 of one batch of nq = 2 np reads.
+// (pairs_impl).  They are declared here and defined once, with the k_pair_* kernels, in
+// sas_pairs.hip; the layout of the join's key is here because k_pair_rescue writes it too.
+// Pair i is reads 2i and 2i + 1 of one batch of nq = 2 np reads.
 //
 //   1. map_select_batch  steps 1..3 of sas_map.hip over the 4 np batch queries (forward read r as
 //                     batch query r, its reverse complement as nq + r): the P sorted proposals
@@ -32,313 +34,16 @@
 //   4. k_pair_finalize one thread per pair: the decoded winner (the forward mate's distance is
 //                     read back from its locus) or the two single-read winners, every per-read
 //                     and per-pair record, and the request of one alignment per read.  Its RESCUE
-//                     instantiation (sas_rescue.hip) puts the rescue winner between the two;
+//                     instantiation (sas_map_pairs_rescue) puts the rescue winner between the two;
 //   5. sas_align_edit over those 2 np alignments, chained on the stream.
 #pragma once
 #include "map_path.hpp"
-
-struct PrTile {  // LDS of one tile's segmented reduction
-    uint64_t mn[MAP_T];   // per segment of the tile
-    uint32_t cnt[MAP_T];
-    uint32_t heads[MAP_CHUNKS], pre[MAP_CHUNKS + 1];
-};
-
-// The segmented reduction of one tile, for the whole workgroup of MAP_BLOCK threads.  Element
-// el = u MAP_BLOCK + tid carries mn[u] (MAP_NONE: nothing) and ct[u]; head[u] starts a segment
-// (element 0 must be a head).  Afterwards sg[u] is the element's segment (its rank in the tile),
-// s.mn / s.cnt hold the segments' minimum and sum, and the number of segments is returned.  The
-// caller puts a __syncthreads() between two tiles.
-template <bool MIN, bool CNT>
-__device__ __forceinline__ uint32_t pr_tile_reduce(PrTile& s, const bool (&valid)[MAP_PER], const bool (&head)[MAP_PER],
-                                                   const uint64_t (&mn)[MAP_PER], const uint32_t (&ct)[MAP_PER],
-                                                   uint32_t (&sg)[MAP_PER]) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t x = tid; x < MAP_T; x += MAP_BLOCK) {
-        if (MIN) s.mn[x] = MAP_NONE;
-        if (CNT) s.cnt[x] = 0;
-    }
-    uint64_t hb[MAP_PER];
-#pragma unroll
-    for (int u = 0; u < MAP_PER; u++) {
-        hb[u] = __ballot(valid[u] && head[u]);
-        if (lane == 0) s.heads[u * 4 + wave] = (uint32_t)__popcll(hb[u]);
-    }
-    __syncthreads();
-    if (tid < MAP_CHUNKS) {  // exclusive scan of the chunks' head counts (half of wave 0)
-        const uint32_t v = s.heads[tid];
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < MAP_CHUNKS; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off);
-            if ((int)tid >= off) inc += o;
-        }
-        s.pre[tid] = inc - v;
-        if (tid == MAP_CHUNKS - 1) s.pre[MAP_CHUNKS] = inc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < MAP_PER; u++) {
-        // the segment's rank in the tile: heads before and at this element, less one
-        sg[u] = valid[u] ? s.pre[u * 4 + wave] + (uint32_t)__popcll(hb[u] & ((2ull << lane) - 1ull)) - 1u : 0xFFFFFFFFu;
-        uint64_t m1 = mn[u];
-        uint32_t c1 = ct[u];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {  // segmented inclusive scan of the wave's 64 elements
-            const uint32_t so = __shfl_up(sg[u], off);
-            const bool take = (int)lane >= off && so == sg[u];
-            if (MIN) {
-                const uint64_t mo = __shfl_up(m1, off);
-                if (take && mo < m1) m1 = mo;
-            }
-            if (CNT) {
-                const uint32_t co = __shfl_up(c1, off);
-                if (take) c1 += co;
-            }
-        }
-        const uint32_t nx = __shfl_down(sg[u], 1);
-        if (valid[u] && sg[u] < MAP_T && (lane == 63 || nx != sg[u])) {  // the last of its segment in this wave
-            if (MIN && m1 != MAP_NONE) atomicMin((unsigned long long*)&s.mn[sg[u]], (unsigned long long)m1);
-            if (CNT && c1) atomicAdd(&s.cnt[sg[u]], c1);
-        }
-    }
-    __syncthreads();
-    return s.pre[MAP_CHUNKS];  // <= the tile's elements
-}
-
-struct PairLoci {
-    const uint64_t* keys;   // P sorted proposals, (batch query << ebits) | end
-    const uint8_t* vals;    // their distances
-    uint64_t P;
-    uint32_t ebits;
-    uint64_t* toff;         // per tile: k_pair_heads writes its heads, the scan turns them into its first locus
-    uint64_t* lmin;         // per locus: the least dist << 56 | end (MAP_NONE before k_pair_loci)
-    uint64_t* lkey;         // per locus: batch query << ebits (k_pair_loci) | e_rep (k_pair_pack)
-    uint8_t* ldist;
-    uint64_t* meta;         // [0] = L, [1] = LF
-    uint64_t nfwd;          // batch queries below it are forward strands
-};
-
-// Proposal p (key, its left neighbour prev) starts a locus: an end of the answer whose
-// predecessor is not
-__device__ __forceinline__ bool pr_locus_head(uint64_t p, uint64_t key, uint64_t prev, uint32_t ebits) {
-    return p == 0 || (prev != key && !((prev >> ebits) == (key >> ebits) && prev + 1 == key));
-}
-
-static __global__ __launch_bounds__(MAP_BLOCK) void k_pair_heads(PairLoci a) {
-    __shared__ uint32_t s_n;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint64_t P = a.P, ntiles = (P + MAP_T - 1) / MAP_T;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)MAP_T;
-        if (tid == 0) s_n = 0;
-        __syncthreads();
-        uint32_t c = 0;
-#pragma unroll
-        for (int u = 0; u < MAP_PER; u++) {
-            const uint64_t p = t0 + u * MAP_BLOCK + tid;
-            bool h = false;
-            if (p < P) h = pr_locus_head(p, a.keys[p], p ? a.keys[p - 1] : 0, a.ebits);
-            c += (uint32_t)__popcll(__ballot(h));
-        }
-        if (lane == 0 && c) atomicAdd(&s_n, c);
-        __syncthreads();
-        if (tid == 0) a.toff[tile] = s_n;
-        __syncthreads();
-    }
-}
-
-static __global__ __launch_bounds__(MAP_BLOCK) void k_pair_loci(PairLoci a) {
-    __shared__ PrTile s;
-    const uint32_t tid = threadIdx.x;
-    const uint64_t P = a.P, ntiles = (P + MAP_T - 1) / MAP_T;
-    const uint64_t emask = (1ull << a.ebits) - 1ull;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)MAP_T;
-        const uint64_t t1 = t0 + MAP_T < P ? t0 + MAP_T : P;
-        const uint32_t n_el = (uint32_t)(t1 - t0);
-        uint64_t kb[MAP_PER], mn[MAP_PER];
-        uint32_t ct[MAP_PER], sg[MAP_PER];
-        bool valid[MAP_PER], head[MAP_PER], own[MAP_PER];
-#pragma unroll
-        for (int u = 0; u < MAP_PER; u++) {
-            const uint32_t el = u * MAP_BLOCK + tid;
-            const uint64_t p = t0 + el;
-            valid[u] = el < n_el;
-            kb[u] = 0;
-            mn[u] = MAP_NONE;
-            ct[u] = 0;
-            head[u] = own[u] = false;
-            if (valid[u]) {
-                const uint64_t key = a.keys[p], prev = p ? a.keys[p - 1] : 0;
-                own[u] = pr_locus_head(p, key, prev, a.ebits);
-                head[u] = el == 0 || own[u];
-                kb[u] = key & ~emask;
-                if (p == 0 || prev != key) mn[u] = ((uint64_t)a.vals[p] << 56) | (key & emask);
-            }
-        }
-        const uint32_t nseg = pr_tile_reduce<true, false>(s, valid, head, mn, ct, sg);
-        // the tile's first element goes on a locus of the tile before it unless it is a head itself
-        const bool first_own = pr_locus_head(t0, a.keys[t0], t0 ? a.keys[t0 - 1] : 0, a.ebits);
-        const bool last_open = t1 < P && !pr_locus_head(t1, a.keys[t1], a.keys[t1 - 1], a.ebits);
-        const uint64_t base = a.toff[tile] - (first_own ? 0u : 1u);
-#pragma unroll
-        for (int u = 0; u < MAP_PER; u++)
-            if (valid[u] && own[u] && sg[u] < MAP_T) a.lkey[base + sg[u]] = kb[u];
-        for (uint32_t sgi = tid; sgi < nseg && sgi < MAP_T; sgi += MAP_BLOCK) {
-            const bool open = (sgi == 0 && !first_own) || (sgi == nseg - 1 && last_open);
-            const uint64_t m1 = s.mn[sgi];
-            if (!open) a.lmin[base + sgi] = m1;
-            else if (m1 != MAP_NONE) atomicMin((unsigned long long*)&a.lmin[base + sgi], (unsigned long long)m1);
-        }
-        __syncthreads();  // the segment slots are reset by the next tile
-    }
-}
-
-// L = the loci of all tiles; LF = the first locus of a reverse strand (the batch-query bits of
-// lkey are complete after k_pair_loci)
-static __global__ void k_pair_meta(PairLoci a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const uint64_t L = a.toff[(a.P + MAP_T - 1) / MAP_T];
-    uint64_t l = 0, h = L;
-    while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if ((a.lkey[mid] >> a.ebits) < a.nfwd) l = mid + 1;
-        else h = mid;
-    }
-    a.meta[0] = L;
-    a.meta[1] = l;
-}
-
-static __global__ void k_pair_pack(PairLoci a) {
-    const uint64_t L = a.toff[(a.P + MAP_T - 1) / MAP_T];
-    const uint64_t emask = (1ull << a.ebits) - 1ull;
-    GRID_STRIDE(i, L < a.P ? L : a.P) {
-        const uint64_t m1 = a.lmin[i];
-        a.lkey[i] |= m1 & emask;
-        a.ldist[i] = (uint8_t)(m1 >> 56);
-    }
-}
 
 // the pass-1 key of a pair: sum << 58 | o << 57 | e_x << 16 | (e_y - window start)
 #define PR_SUM_SHIFT 58
 #define PR_O_SHIFT 57
 #define PR_EX_SHIFT 16
 #define PR_EX_MASK ((1ull << 41) - 1ull)
-
-struct PairJoin {
-    const uint64_t* lkey;
-    const uint8_t* ldist;
-    const uint64_t* meta;
-    MmQueries B;            // the batch (the forward mate's length)
-    uint64_t nfwd, n;       // 2 np; the text's chars
-    uint32_t ebits, min_frag, max_frag;
-    uint64_t* pmin;         // per pair: the least pass-1 key (MAP_NONE before pass 1)
-    uint64_t* pcnt;         // per pair: proper candidates (0 before pass 1)
-    uint64_t* pbest;        // per pair: those at the least sum (0 before pass 2)
-};
-
-template <int PASS>
-__global__ __launch_bounds__(MAP_BLOCK) void k_pair_join(PairJoin a) {
-    __shared__ PrTile s;
-    __shared__ uint64_t s_q[MAP_T];  // per segment: its pair
-    const uint32_t tid = threadIdx.x;
-    const uint64_t L = a.meta[0], LF = a.meta[1], ntiles = (LF + MAP_T - 1) / MAP_T;
-    const uint64_t emask = (1ull << a.ebits) - 1ull;
-    const int64_t spread = (int64_t)a.max_frag - (int64_t)a.min_frag;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)MAP_T;
-        const uint64_t t1 = t0 + MAP_T < LF ? t0 + MAP_T : LF;
-        const uint32_t n_el = (uint32_t)(t1 - t0);
-        uint64_t pr[MAP_PER], mn[MAP_PER];
-        uint32_t ct[MAP_PER], sg[MAP_PER];
-        bool valid[MAP_PER], head[MAP_PER];
-#pragma unroll
-        for (int u = 0; u < MAP_PER; u++) {
-            const uint32_t el = u * MAP_BLOCK + tid;
-            const uint64_t p = t0 + el;
-            valid[u] = el < n_el;
-            pr[u] = 0;
-            mn[u] = MAP_NONE;
-            ct[u] = 0;
-            head[u] = false;
-            if (!valid[u]) continue;
-            const uint64_t key = a.lkey[p], b = key >> a.ebits, ex = key & emask;
-            const uint32_t dx = a.ldist[p];
-            pr[u] = b >> 1;
-            head[u] = el == 0 || (a.lkey[p - 1] >> (a.ebits + 1)) != pr[u];
-            if (b >= a.nfwd) continue;
-            const int64_t lo = (int64_t)ex - (int64_t)a.B.len(b) + (int64_t)a.min_frag, hi = lo + spread;
-            if (hi < 0 || lo > (int64_t)a.n) continue;
-            uint32_t need = 0;
-            if (PASS == 2) {
-                const uint64_t pm = a.pmin[pr[u]];
-                if (pm == MAP_NONE || (uint32_t)(pm >> PR_SUM_SHIFT) < dx) continue;
-                need = (uint32_t)(pm >> PR_SUM_SHIFT) - dx;
-            }
-            // the partner window: the reverse-strand loci of the other mate with lo <= e_y <= hi
-            const uint64_t bv = (a.nfwd + (b ^ 1ull)) << a.ebits;
-            const uint64_t klo = bv | (uint64_t)(lo < 0 ? 0 : lo);
-            const uint64_t khi = bv | (hi > (int64_t)a.n ? a.n : (uint64_t)hi);
-            uint64_t l = LF, h = L;
-            while (l < h) {  // the first locus with klo <= lkey
-                const uint64_t mid = (l + h) >> 1;
-                if (a.lkey[mid] < klo) l = mid + 1;
-                else h = mid;
-            }
-            const uint64_t w0 = l;
-            // loci are at least 2 apart: the window holds at most spread / 2 + 1 of them
-            h = w0 + (uint64_t)(spread / 2 + 2);
-            if (h > L) h = L;
-            while (l < h) {  // the first locus with khi < lkey
-                const uint64_t mid = (l + h) >> 1;
-                if (a.lkey[mid] <= khi) l = mid + 1;
-                else h = mid;
-            }
-            const uint64_t w1 = l;
-            if (PASS == 1) {
-                ct[u] = (uint32_t)(w1 - w0);
-                uint64_t best = MAP_NONE;  // (D_y, e_y - lo) of the window
-                for (uint64_t j = w0; j < w1; j++) {
-                    const uint64_t v = ((uint64_t)a.ldist[j] << 16) | (uint64_t)((int64_t)(a.lkey[j] & emask) - lo);
-                    best = v < best ? v : best;
-                }
-                if (w1 > w0)
-                    mn[u] = ((uint64_t)(dx + (uint32_t)(best >> 16)) << PR_SUM_SHIFT) | ((b & 1ull) << PR_O_SHIFT) |
-                            (ex << PR_EX_SHIFT) | (best & 0xFFFFull);
-            } else {
-                uint32_t c = 0;
-                for (uint64_t j = w0; j < w1; j++) c += a.ldist[j] == need ? 1u : 0u;
-                ct[u] = c;
-            }
-        }
-        const uint32_t nseg = pr_tile_reduce<PASS == 1, true>(s, valid, head, mn, ct, sg);
-#pragma unroll
-        for (int u = 0; u < MAP_PER; u++)
-            if (valid[u] && head[u] && sg[u] < MAP_T) s_q[sg[u]] = pr[u];
-        __syncthreads();
-        for (uint32_t sgi = tid; sgi < nseg && sgi < MAP_T; sgi += MAP_BLOCK) {
-            const uint64_t pair = s_q[sgi];
-            if (pair >= (a.nfwd >> 1)) continue;
-            // a segment that goes on in a neighbouring tile shares its slot with that tile
-            const bool open = (sgi == 0 && t0 > 0 && (a.lkey[t0 - 1] >> (a.ebits + 1)) == pair) ||
-                              (sgi == nseg - 1 && t1 < LF && (a.lkey[t1] >> (a.ebits + 1)) == pair);
-            const uint64_t m1 = s.mn[sgi], c1 = s.cnt[sgi];
-            if (PASS == 1) {
-                if (!open) {
-                    a.pmin[pair] = m1;
-                    a.pcnt[pair] = c1;
-                } else {
-                    if (m1 != MAP_NONE) atomicMin((unsigned long long*)&a.pmin[pair], (unsigned long long)m1);
-                    if (c1) atomicAdd((unsigned long long*)&a.pcnt[pair], (unsigned long long)c1);
-                }
-            } else {
-                if (!open) a.pbest[pair] = c1;
-                else if (c1) atomicAdd((unsigned long long*)&a.pbest[pair], (unsigned long long)c1);
-            }
-        }
-        __syncthreads();  // the segment slots are reset by the next tile
-    }
-}
 
 struct PairOut {
     void* end;
@@ -365,354 +70,27 @@ struct PairCall {
     bool rescue;
 };
 
-struct PairFin {
-    MmQueries B;            // the batch
-    uint64_t np, n;
-    uint32_t ebits, min_frag;
-    const uint64_t* kmin;   // the single-read slots
-    const uint64_t* nloci;
-    const uint64_t* nbest;
-    const uint8_t* efl;
-    const uint64_t* lkey;   // the loci (null: none)
-    const uint8_t* ldist;
-    const uint64_t* meta;
-    const uint64_t* pmin;   // the pairs' slots
-    const uint64_t* pcnt;
-    const uint64_t* pbest;
-    const uint64_t* rmin;   // RESCUE: per pair the least rescue key (MAP_NONE: none), in the join's layout,
-    const uint64_t* rcnt;   // and the candidate runs of its anchors' windows (both null: rescue is off)
-    uint64_t max_anchors;
-    PairOut o;
-    uint64_t* aoff;         // the alignment request: 2 np + 1 offsets 0 .. 2 np,
-    uint64_t* aqoff;        // each read's chosen strand in the batch
-    uint32_t* aqlen;        // and its length (0: no alignment)
-};
-
-// The first locus of lkey[lo .. hi) that is not below `want`
-__device__ __forceinline__ uint64_t pr_locus_lower(const uint64_t* __restrict__ lkey, uint64_t lo, uint64_t hi,
-                                                   uint64_t want) {
-    uint64_t l = lo, h = hi;
-    while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if (lkey[mid] < want) l = mid + 1;
-        else h = mid;
-    }
-    return l;
-}
-
-// RESCUE (sas_map_pairs_rescue): a pair without a proper candidate takes the rescue winner when
-// there is one; the existing instantiation reads none of the rescue fields
-template <bool U32, bool RESCUE>
-__global__ void k_pair_finalize(PairFin a) {
-    const uint64_t nq = 2 * a.np;
-    GRID_STRIDE(i, a.np + 1) {
-        if (i == a.np) {
-            a.aoff[nq] = nq;
-            continue;
-        }
-        const uint64_t pm = a.pmin[i];
-        const bool proper = pm != MAP_NONE;
-        uint64_t f = 0, ex = 0, ey = 0;
-        uint32_t dx = 0, dy = 0;
-        bool rescued = false, skipped = false;
-        uint64_t got = nq;  // the read that the rescue placed
-        if (RESCUE && !proper && a.max_anchors) {
-            const uint64_t anchors = a.nloci[2 * i] + a.nloci[2 * i + 1] + a.nloci[nq + 2 * i] + a.nloci[nq + 2 * i + 1];
-            skipped = anchors > a.max_anchors;
-            const uint64_t rm = a.rmin ? a.rmin[i] : MAP_NONE;
-            if (rm != MAP_NONE) {
-                rescued = true;
-                const uint32_t sum = (uint32_t)(rm >> PR_SUM_SHIFT);
-                f = 2 * i + ((rm >> PR_O_SHIFT) & 1ull);
-                ex = (rm >> PR_EX_SHIFT) & PR_EX_MASK;
-                ey = (uint64_t)((int64_t)ex - (int64_t)a.B.len(f) + (int64_t)a.min_frag + (int64_t)(rm & 0xFFFFull));
-                // the anchor's side: (f, e_x) is the representative of a forward locus, or else
-                // (v, e_y) that of a reverse one (both at once would be a proper candidate)
-                const uint64_t L = a.meta[0], LF = a.meta[1], v = 4 * i + 1 - f;
-                const uint64_t wx = (f << a.ebits) | ex, wy = ((nq + v) << a.ebits) | ey;
-                const uint64_t lx = pr_locus_lower(a.lkey, 0, LF, wx);
-                if (lx < LF && a.lkey[lx] == wx) {
-                    dx = a.ldist[lx];
-                    dy = sum - dx;
-                    got = v;
-                } else {
-                    const uint64_t ly = pr_locus_lower(a.lkey, LF, L, wy);
-                    dy = a.ldist[ly < L ? ly : L - 1];  // a winner's anchor exists: L > 0
-                    dx = sum - dy;
-                    got = f;
-                }
-            }
-        }
-        if (proper) {
-            const uint32_t sum = (uint32_t)(pm >> PR_SUM_SHIFT);
-            f = 2 * i + ((pm >> PR_O_SHIFT) & 1ull);
-            ex = (pm >> PR_EX_SHIFT) & PR_EX_MASK;
-            ey = (uint64_t)((int64_t)ex - (int64_t)a.B.len(f) + (int64_t)a.min_frag + (int64_t)(pm & 0xFFFFull));
-            // the forward mate's distance: that of its locus, whose representative is e_x
-            const uint64_t want = (f << a.ebits) | ex;
-            const uint64_t LF = a.meta[1];
-            uint64_t l = 0, h = LF;
-            while (l < h) {
-                const uint64_t mid = (l + h) >> 1;
-                if (a.lkey[mid] < want) l = mid + 1;
-                else h = mid;
-            }
-            dx = a.ldist[l < LF ? l : LF - 1];  // a winner's locus exists: LF > 0
-            dy = sum - dx;
-        }
-        for (uint64_t r = 2 * i; r < 2 * i + 2; r++) {
-            const MapBest s = map_best_of(r, nq, 2u, SAS_MAP_FWD | SAS_MAP_REV, a.kmin, a.nloci, a.nbest, a.efl);
-            bool mapped = s.best != MAP_NONE;
-            uint64_t e = mapped ? s.best & ((1ull << 55) - 1ull) : a.n, bb = s.bb;
-            uint32_t d = mapped ? (uint32_t)(s.best >> 56) : SAS_AL_NONE_DIST;
-            uint32_t strand = mapped ? (uint32_t)((s.best >> 55) & 1ull) : 0u;
-            if (proper || (RESCUE && rescued)) {
-                mapped = true;
-                strand = r == f ? 0u : 1u;
-                e = strand ? ey : ex;
-                d = strand ? dy : dx;
-                bb = strand ? nq + r : r;
-            }
-            if (U32) static_cast<uint32_t*>(a.o.end)[r] = (uint32_t)e;
-            else static_cast<uint64_t*>(a.o.end)[r] = e;
-            a.o.dist[r] = (uint8_t)d;
-            if (a.o.strand) a.o.strand[r] = (uint8_t)strand;
-            if (a.o.nbest) a.o.nbest[r] = map_clamp32(s.nbst);
-            if (a.o.nloci) a.o.nloci[r] = map_clamp32(s.nl);
-            if (a.o.qflags) a.o.qflags[r] = (uint8_t)(s.fl | (RESCUE && r == got ? SAS_MAP_RESCUED : 0u));
-            a.aoff[r] = r;
-            a.aqoff[r] = a.B.off(bb);
-            a.aqlen[r] = mapped ? a.B.len(bb) : 0u;
-        }
-        if (a.o.pflags)
-            a.o.pflags[i] = (uint8_t)((proper ? SAS_PAIR_PROPER : 0u) | (RESCUE && rescued ? SAS_PAIR_RESCUED : 0u) |
-                                      (RESCUE && skipped ? SAS_PAIR_RESCUE_SKIPPED : 0u));
-        if (a.o.npairs) a.o.npairs[i] = map_clamp32(a.pcnt[i]);
-        if (a.o.nbestpairs) a.o.nbestpairs[i] = map_clamp32(a.pbest[i]);
-        if (RESCUE && a.o.nrescue) a.o.nrescue[i] = a.rcnt ? map_clamp32(a.rcnt[i]) : 0u;
-    }
-}
-
 // Steps 1..3: the batch, its loci and the join's slots.  The scratch lives as long as the state
 struct PairState {
     MapState ms;
     MmPoolBuf pslots, meta, toff, lmin, lkey, ldist;
 };
 
-// All arrays on the device; Q: the caller's 2 np reads
-static int pair_join_batch(const sas_index* x, const MmQueries& Q, const PairCall& c, hipStream_t st, uint32_t flags,
-                           PairState& ps) {
-    const uint64_t nq = Q.nq, np = nq / 2;
-    const uint32_t min_frag = c.min_frag, max_frag = c.max_frag;
-    hipMemPool_t pool;
-    TRY(sas_scratch_pool(x, &pool));
-    const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
-    // 1. the batch of both strands, its sorted proposals, the single-read slots
-    MapState& ms = ps.ms;
-    TRY(map_select_batch(x, Q, c.k, c.max_seed_hits, SAS_MAP_FWD | SAS_MAP_REV, st, flags, ms));
-    const MmQueries& B = ms.B;
-    const EdState& s = ms.s;
-    // the pairs' slots and the loci scratch, sized from P (the locus total stays on the device)
-    MmPoolBuf &pslots = ps.pslots, &meta = ps.meta, &toff = ps.toff, &lmin = ps.lmin, &lkey = ps.lkey,
-              &ldist = ps.ldist;
-    TRY(pslots.alloc(pool, 3 * np * 8, st));
-    HIP_TRY(hipMemsetAsync(pslots.p, 0xFF, np * 8, st));
-    HIP_TRY(hipMemsetAsync(pslots.as<uint64_t>() + np, 0, 2 * np * 8, st));
-    TRY(meta.alloc(pool, 16, st));
-    HIP_TRY(hipMemsetAsync(meta.p, 0, 16, st));
-    if (s.P) {
-        const uint64_t tiles = (s.P + MAP_T - 1) / MAP_T;
-        const dim3 tgrid((unsigned)tile_grid(std::min<uint64_t>(tiles, (uint64_t)x->num_cus * MAP_BPC)));
-        TRY(toff.alloc(pool, (tiles + 1) * 8, st));
-        TRY(lmin.alloc(pool, s.P * 8, st));
-        TRY(lkey.alloc(pool, s.P * 8, st));
-        TRY(ldist.alloc(pool, s.P, st));
-        HIP_TRY(hipMemsetAsync(toff.p, 0, (tiles + 1) * 8, st));
-        HIP_TRY(hipMemsetAsync(lmin.p, 0xFF, s.P * 8, st));
-        // 2. the loci
-        PairLoci a{};
-        a.keys = s.skeys;
-        a.vals = s.svals;
-        a.P = s.P;
-        a.ebits = s.ebits;
-        a.toff = toff.as<uint64_t>();
-        a.lmin = lmin.as<uint64_t>();
-        a.lkey = lkey.as<uint64_t>();
-        a.ldist = ldist.as<uint8_t>();
-        a.meta = meta.as<uint64_t>();
-        a.nfwd = nq;
-        hipLaunchKernelGGL(k_pair_heads, tgrid, dim3(MAP_BLOCK), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        TRY(mm_scan(pool, st, a.toff, a.toff, tiles + 1));
-        hipLaunchKernelGGL(k_pair_loci, tgrid, dim3(MAP_BLOCK), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_pair_meta, dim3(1), dim3(64), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_pair_pack, grid(s.P), dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        // 3. the join
-        PairJoin j{};
-        j.lkey = a.lkey;
-        j.ldist = a.ldist;
-        j.meta = a.meta;
-        j.B = B;
-        j.nfwd = nq;
-        j.n = x->n;
-        j.ebits = s.ebits;
-        j.min_frag = min_frag;
-        j.max_frag = max_frag;
-        j.pmin = pslots.as<uint64_t>();
-        j.pcnt = j.pmin + np;
-        j.pbest = j.pmin + 2 * np;
-        hipLaunchKernelGGL(k_pair_join<1>, tgrid, dim3(MAP_BLOCK), 0, st, j);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_pair_join<2>, tgrid, dim3(MAP_BLOCK), 0, st, j);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
+// Steps 1..3.  All arrays on the device; Q: the caller's 2 np reads
+int pair_join_batch(const sas_index* x, const MmQueries& Q, const PairCall& c, hipStream_t st, uint32_t flags,
+                    PairState& ps);
 
 // Steps 4 and 5 behind pair_join_batch.  RESCUE: rmin / rcnt are the rescue's slots (null: it
-// found no work) and the alignments are made with k_rescue
+// found no work) and the alignments are made with k_rescue.  Instantiated in sas_pairs.hip
 template <bool RESCUE>
-static int pair_finish(const sas_index* x, const PairCall& c, PairState& ps, const uint64_t* rmin, const uint64_t* rcnt,
-                       const PairOut& o, hipStream_t st, uint32_t flags) {
-    MapState& ms = ps.ms;
-    const MmQueries& B = ms.B;
-    const EdState& s = ms.s;
-    const uint64_t nq = B.nq / 2, np = nq / 2;
-    hipMemPool_t pool;
-    TRY(sas_scratch_pool(x, &pool));
-    const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
-    MmPoolBuf &pslots = ps.pslots, &meta = ps.meta, &lkey = ps.lkey, &ldist = ps.ldist;
-    MmPoolBuf areq;
-    // 4. the records and the alignment request
-    const bool align = o.start || o.nruns || o.runs;
-    const bool u32 = (flags & SAS_LOCATE_U32) != 0;
-    const uint64_t esz = u32 ? 4 : 8;
-    TRY(areq.alloc(pool, (nq + 1) * 8 + nq * 8 + nq * 4 + (o.start ? 0 : nq * esz), st));
-    PairFin f{};
-    f.B = B;
-    f.np = np;
-    f.n = x->n;
-    f.ebits = s.ebits;
-    f.min_frag = c.min_frag;
-    f.rmin = rmin;
-    f.rcnt = rcnt;
-    f.max_anchors = c.max_anchors;
-    f.kmin = ms.kmin;
-    f.nloci = ms.nloci;
-    f.nbest = ms.nbest;
-    f.efl = ms.efl.as<uint8_t>();
-    f.lkey = lkey.as<uint64_t>();
-    f.ldist = ldist.as<uint8_t>();
-    f.meta = meta.as<uint64_t>();
-    f.pmin = pslots.as<uint64_t>();
-    f.pcnt = f.pmin + np;
-    f.pbest = f.pmin + 2 * np;
-    f.o = o;
-    f.aoff = areq.as<uint64_t>();
-    f.aqoff = f.aoff + nq + 1;
-    void* scratch_start = f.aqoff + nq;                  // 8-byte aligned; unused when out_start is given
-    f.aqlen = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch_start) + (o.start ? 0 : nq * esz));
-    if (u32) hipLaunchKernelGGL((k_pair_finalize<true, RESCUE>), grid(np + 1), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL((k_pair_finalize<false, RESCUE>), grid(np + 1), dim3(256), 0, st, f);
-    HIP_TRY(hipGetLastError());
-    // 5. one alignment per read (bytes were validated by the range search when asked for)
-    if (!align) return 0;
-    return sas_align_edit(x, B.qbytes, f.aqoff, f.aqlen, nq, RESCUE ? c.k_rescue : c.k, f.aoff, o.end, nq,
-                          o.start ? o.start : scratch_start, nullptr, o.nruns, o.runs, st,
-                          SAS_DEVICE_PTRS | (flags & SAS_LOCATE_U32));
-}
+int pair_finish(const sas_index* x, const PairCall& c, PairState& ps, const uint64_t* rmin, const uint64_t* rcnt,
+                const PairOut& o, hipStream_t st, uint32_t flags);
 
 // The device path of one call: all arrays on the device; Q: the caller's 2 np reads
 typedef int (*PairDevice)(const sas_index* x, const MmQueries& Q, const PairCall& c, const PairOut& o, hipStream_t st,
                           uint32_t flags);
 
-static int pairs_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                      const uint32_t* qlen, uint32_t m, uint64_t np, const PairCall& c, PairDevice device,
-                      const PairOut& o, void* stream, uint32_t flags) {
-    const std::string w(fn);
-    const uint32_t k = c.k, min_frag = c.min_frag, max_frag = c.max_frag;
-    if (min_frag > max_frag) SAS_FAIL(EINVAL, w + ": min_frag must not exceed max_frag");
-    if (max_frag - min_frag > SAS_PAIR_MAX_SPREAD)
-        SAS_FAIL(EINVAL, w + ": max_frag - min_frag must not exceed SAS_PAIR_MAX_SPREAD (" +
-                             std::to_string(SAS_PAIR_MAX_SPREAD) + ")");
-    if (c.rescue && (c.k_rescue < k || c.k_rescue > MM_MAX_K))
-        SAS_FAIL(EINVAL, w + ": k_rescue must be k.." + std::to_string(MM_MAX_K));
-    if (!x) SAS_FAIL(EINVAL, w + ": null index");
-    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
-    if (x->tag_lines || x->sa_w == 8)
-        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
-    if (x->rank_lo != 0 || x->sa_n != x->n)
-        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
-    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
-    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
-        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
-    // the (batch query, end) sort key of two mates on two strands
-    if (np >= (1ull << 61) || ed_bits(x->n) + (np ? ed_bits(4 * np - 1) : 0) > 64)
-        SAS_FAIL(EINVAL, w + ": " + std::to_string(np) + " pairs on two strands and a text of " + std::to_string(x->n) +
-                             " chars do not fit the 64-bit (query, end) sort key: split the batch");
-    TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
-    if (np == 0) return 0;
-    if (!qbytes || (ragged && (!qoff || !qlen)) || !o.end || !o.dist) SAS_FAIL(EINVAL, w + ": null argument");
-    HIP_TRY(hipSetDevice(x->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint64_t nq = 2 * np;
-    if (flags & SAS_DEVICE_PTRS) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        return device(x, Q, c, o, st, flags);
-    }
-    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
-        span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
-    }
-    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8, stride = 2 * (uint64_t)(c.rescue ? c.k_rescue : k) + 1;
-    DevBuf dq, dqoff, dqlen, dend, dstart, ddist, dstrand, dnbest, dnloci, dnruns, druns, dfl, dpfl, dnp, dnbp, dnr;
-    TRY(dq.alloc(span + 64, "pair queries"));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(dqoff.alloc(nq * 8, "pair query offsets"));
-        TRY(dqlen.alloc(nq * 4, "pair query lengths"));
-        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-    }
-    TRY(dend.alloc(nq * esz, "pair ends"));
-    TRY(ddist.alloc(nq, "pair distances"));
-    if (o.start) TRY(dstart.alloc(nq * esz, "pair starts"));
-    if (o.strand) TRY(dstrand.alloc(nq, "pair strands"));
-    if (o.nbest) TRY(dnbest.alloc(nq * 4, "pair best counts"));
-    if (o.nloci) TRY(dnloci.alloc(nq * 4, "pair locus counts"));
-    if (o.nruns) TRY(dnruns.alloc(nq, "pair run counts"));
-    if (o.runs) TRY(druns.alloc(nq * stride * 2, "pair runs"));
-    if (o.qflags) TRY(dfl.alloc(nq, "pair query flags"));
-    if (o.pflags) TRY(dpfl.alloc(np, "pair flags"));
-    if (o.npairs) TRY(dnp.alloc(np * 4, "pair candidate counts"));
-    if (o.nbestpairs) TRY(dnbp.alloc(np * 4, "pair best candidate counts"));
-    if (o.nrescue) TRY(dnr.alloc(np * 4, "pair rescue counts"));
-    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
-    const PairOut d{dend.p, dstart.p, ddist.as<uint8_t>(), dstrand.as<uint8_t>(), dnbest.as<uint32_t>(),
-                    dnloci.as<uint32_t>(), dnruns.as<uint8_t>(), druns.as<uint16_t>(), dfl.as<uint8_t>(),
-                    dpfl.as<uint8_t>(), dnp.as<uint32_t>(), dnbp.as<uint32_t>(), dnr.as<uint32_t>()};
-    TRY(device(x, Q, c, d, st, flags | SAS_VALIDATE));
-    HIP_TRY(hipMemcpyAsync(o.end, dend.p, nq * esz, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(o.dist, ddist.p, nq, hipMemcpyDeviceToHost, st));
-    if (o.start) HIP_TRY(hipMemcpyAsync(o.start, dstart.p, nq * esz, hipMemcpyDeviceToHost, st));
-    if (o.strand) HIP_TRY(hipMemcpyAsync(o.strand, dstrand.p, nq, hipMemcpyDeviceToHost, st));
-    if (o.nbest) HIP_TRY(hipMemcpyAsync(o.nbest, dnbest.p, nq * 4, hipMemcpyDeviceToHost, st));
-    if (o.nloci) HIP_TRY(hipMemcpyAsync(o.nloci, dnloci.p, nq * 4, hipMemcpyDeviceToHost, st));
-    if (o.nruns) HIP_TRY(hipMemcpyAsync(o.nruns, dnruns.p, nq, hipMemcpyDeviceToHost, st));
-    if (o.runs) HIP_TRY(hipMemcpyAsync(o.runs, druns.p, nq * stride * 2, hipMemcpyDeviceToHost, st));
-    if (o.qflags) HIP_TRY(hipMemcpyAsync(o.qflags, dfl.p, nq, hipMemcpyDeviceToHost, st));
-    if (o.pflags) HIP_TRY(hipMemcpyAsync(o.pflags, dpfl.p, np, hipMemcpyDeviceToHost, st));
-    if (o.npairs) HIP_TRY(hipMemcpyAsync(o.npairs, dnp.p, np * 4, hipMemcpyDeviceToHost, st));
-    if (o.nbestpairs) HIP_TRY(hipMemcpyAsync(o.nbestpairs, dnbp.p, np * 4, hipMemcpyDeviceToHost, st));
-    if (o.nrescue) HIP_TRY(hipMemcpyAsync(o.nrescue, dnr.p, np * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
+// The argument checks and the host-pointer path of a paired-end call around its device path
+int pairs_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
+               const uint32_t* qlen, uint32_t m, uint64_t np, const PairCall& c, PairDevice device, const PairOut& o,
+               void* stream, uint32_t flags);

@@ -329,38 +329,23 @@ static int align_impl(const char* fn, const sas_index* x, const uint8_t* qbytes,
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
     const uint64_t count = std::min(na, off[nq]);
     if (count == 0) return 0;
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
-        span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
-    }
     const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8;
-    DevBuf dq, dqoff, dqlen, doff, dend, dstart, ddist, dnr, druns;
-    TRY(dq.alloc(span + 64, "align queries"));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(dqoff.alloc(nq * 8, "align query offsets"));
-        TRY(dqlen.alloc(nq * 4, "align query lengths"));
-        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-    }
-    TRY(doff.alloc((nq + 1) * 8, "align offsets"));
-    TRY(dend.alloc(count * esz, "align ends"));
-    HIP_TRY(hipMemcpy(doff.p, off, (nq + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dend.p, end, count * esz, hipMemcpyHostToDevice));
-    TRY(dstart.alloc(count * esz, "align starts"));
-    if (out_dist) TRY(ddist.alloc(count, "align distances"));
-    if (out_nruns) TRY(dnr.alloc(count, "align run counts"));
-    if (out_runs) TRY(druns.alloc(count * stride * 2, "align runs"));
-    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
-    TRY(al_device(fn, x, Q, k, doff.as<uint64_t>(), dend.p, count, dstart.p, out_dist ? ddist.as<uint8_t>() : nullptr,
-                  out_nruns ? dnr.as<uint8_t>() : nullptr, out_runs ? druns.as<uint16_t>() : nullptr, st, flags,
-                  true));
-    HIP_TRY(hipMemcpyAsync(out_start, dstart.p, count * esz, hipMemcpyDeviceToHost, st));
-    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, ddist.p, count, hipMemcpyDeviceToHost, st));
-    if (out_nruns) HIP_TRY(hipMemcpyAsync(out_nruns, dnr.p, count, hipMemcpyDeviceToHost, st));
-    if (out_runs) HIP_TRY(hipMemcpyAsync(out_runs, druns.p, count * stride * 2, hipMemcpyDeviceToHost, st));
+    HostQueries hq;
+    HostOutputs ho;
+    DevBuf doff, dend;
+    MmQueries Q;
+    TRY(hq.stage("align", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
+    TRY(host_copy_in(doff, off, (nq + 1) * 8, "align offsets"));
+    TRY(host_copy_in(dend, end, count * esz, "align ends"));
+    void* dstart;
+    uint8_t *ddist, *dnr;
+    uint16_t* druns;
+    TRY(ho.twin(out_start, count * esz, "align starts", &dstart));
+    TRY(ho.twin(out_dist, count, "align distances", &ddist));
+    TRY(ho.twin(out_nruns, count, "align run counts", &dnr));
+    TRY(ho.twin(out_runs, count * stride * 2, "align runs", &druns));
+    TRY(al_device(fn, x, Q, k, doff.as<uint64_t>(), dend.p, count, dstart, ddist, dnr, druns, st, flags, true));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

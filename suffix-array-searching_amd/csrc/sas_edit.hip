@@ -8,8 +8,9 @@
 // position pv, and with s0 = pv - b_j (signed) the alignment ends in [s0 + m - k, s0 + m + k].
 // A candidate is one occurrence of one piece:
 //
-//   1. k_mm_pieces, 2. sas_search_range, 4. sas_locate_offsets: as in sas_mismatch.hip;
-//   3. k_ed_gate       empties the range of every piece that occurs more than max_seed_hits
+//   1. k_mm_pieces, 2. sas_search_range, 4. sas_locate_offsets: as in sas_mismatch.hip
+//                      (seed_candidates, seed_verify.hip);
+//   3. k_seed_gate     empties the range of every piece that occurs more than max_seed_hits
 //                      times, and every piece of a query with m <= k or m > SAS_ED_MAX_M; writes
 //                      the per-query flags;
 //   5. k_ed_verify     output-centric over the C candidates (mm_tile_candidates).  Per candidate
@@ -47,27 +48,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-
-// One thread per query: skipped seeds, short and long queries lose their ranges
-__global__ void k_ed_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint64_t* __restrict__ lo,
-                          uint64_t* __restrict__ hi, uint8_t* __restrict__ qflags) {
-    GRID_STRIDE(q, Q.nq) {
-        const uint32_t m = Q.len(q);
-        uint32_t fl = m < kp1 ? SAS_ED_SHORT : (m > SAS_ED_MAX_M ? SAS_ED_LONG : 0u);
-        const bool none = fl != 0;
-        for (uint32_t j = 0; j < kp1; j++) {
-            const uint64_t i = q * kp1 + j;
-            const uint64_t cnt = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
-            const bool over = !none && max_seed_hits && cnt > max_seed_hits;
-            if (over) fl |= SAS_ED_TRUNCATED;
-            if (over || none) {
-                lo[i] = 0;
-                hi[i] = 0;
-            }
-        }
-        qflags[q] = (uint8_t)fl;
-    }
-}
 
 struct EdArgs {
     const uint64_t* tw;
@@ -251,11 +231,6 @@ extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
     return ed_last_dedup_ms;
 }
 
-struct EdEvent {  // destroyed on every way out
-    hipEvent_t e = nullptr;
-    ~EdEvent() { if (e) (void)hipEventDestroy(e); }
-};
-
 template <int NW>
 static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, const EdArgs& a) {
     if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW>), grid, dim3(MM_BLOCK), 0, st, a);
@@ -269,42 +244,26 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     const uint32_t kp1 = k + 1;
     const uint64_t nq = Q.nq, np = nq * kp1;
     s.ebits = ed_bits(x->n);
-    TRY(sas_scratch_pool(x, &s.pool));
-    TRY(s.poff.alloc(s.pool, np * 8, st));
-    TRY(s.plen.alloc(s.pool, np * 4, st));
-    TRY(s.lohi.alloc(s.pool, np * 16, st));
-    TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
-    if (!out_qflags) {
-        TRY(s.qfl.alloc(s.pool, nq, st));
-        out_qflags = s.qfl.as<uint8_t>();
-    }
-    uint64_t* lo = s.lohi.as<uint64_t>();
-    uint64_t* hi = lo + np;
-    const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
     const auto nothing = [&]() {
         HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
         if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
         return 0;
     };
-    hipLaunchKernelGGL(k_mm_pieces, grid(np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(), s.plen.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
-    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, lo, hi, st, rflags));
-    hipLaunchKernelGGL(k_ed_gate, grid(nq), dim3(256), 0, st, Q, kp1, max_seed_hits, lo, hi, out_qflags);
-    HIP_TRY(hipGetLastError());
-    TRY(sas_locate_offsets(x, lo, hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS));
-    HIP_TRY(hipMemcpyAsync(&s.C, s.coff.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, st));
+    // 1 to 4: a query of more than SAS_ED_MAX_M chars gets no seeds
+    TRY(seed_candidates(x, Q, k, max_seed_hits, SAS_ED_MAX_M, false, out_qflags, st, flags, s.seed));
+    hipMemPool_t pool = s.seed.pool;
+    uint64_t* coff = s.seed.coff.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(&s.C, coff + np, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t C = s.C;
     ed_last_candidates = C;
     ed_last_verify_ms = ed_last_dedup_ms = -1.0;
     ed_last_proposals = 0;
     if (C == 0) return nothing();
-    TRY(s.mask.alloc(s.pool, (C + 1) * 4, st));
-    TRY(s.kbase.alloc(s.pool, C * 8, st));
-    TRY(s.dists.alloc(s.pool, C * 16, st));
-    TRY(s.pscan.alloc(s.pool, (C + 1) * 8, st));
+    TRY(s.mask.alloc(pool, (C + 1) * 4, st));
+    TRY(s.kbase.alloc(pool, C * 8, st));
+    TRY(s.dists.alloc(pool, C * 16, st));
+    TRY(s.pscan.alloc(pool, (C + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(s.mask.as<uint32_t>() + C, 0, 4, st));
     EdArgs a{};
     a.tw = x->text_w;
@@ -313,8 +272,8 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     a.Q = Q;
     a.k = k;
     a.ebits = s.ebits;
-    a.lo = lo;
-    a.coff = s.coff.as<uint64_t>();
+    a.lo = s.seed.lo;
+    a.coff = coff;
     a.np = np;
     a.C = C;
     a.mask = s.mask.as<uint32_t>();
@@ -323,42 +282,30 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     uint64_t blocks = (C + MM_T - 1) / MM_T;
     if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
     const dim3 vgrid((unsigned)tile_grid(blocks));
-    EdEvent ev0, ev1;
-    const bool timing = ed_timing();
-    if (timing) {
-        HIP_TRY(hipEventCreate(&ev0.e));
-        HIP_TRY(hipEventCreate(&ev1.e));
-        HIP_TRY(hipEventRecord(ev0.e, st));
-    }
-    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
+    SeedTimer timer(ed_timing(), st);
+    TRY(timer.start());
     // fixed-length batches: the word count from m (a longer m is gated: any kernel serves)
     if (Q.qoff) ed_launch_verify<0>(x, vgrid, st, a);
     else if (Q.m <= 64) ed_launch_verify<1>(x, vgrid, st, a);
     else if (Q.m <= 128) ed_launch_verify<2>(x, vgrid, st, a);
     else ed_launch_verify<4>(x, vgrid, st, a);
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        ed_last_verify_ms = ms;
-    }
+    TRY(timer.stop(&ed_last_verify_ms));
     // proposals: one per accepted end of every candidate
-    TRY(mm_scan(s.pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
+    TRY(mm_scan(pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
                 s.pscan.as<uint64_t>(), C + 1));
     HIP_TRY(hipMemcpyAsync(&s.P, s.pscan.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t P = s.P;
     ed_last_proposals = P;
     if (P == 0) return nothing();
-    if (timing) HIP_TRY(hipEventRecord(e0, st));
-    TRY(s.keys.alloc(s.pool, 2 * P * 8, st));
-    TRY(s.vals.alloc(s.pool, 2 * P, st));
-    TRY(s.uscan.alloc(s.pool, (P + 1) * 8, st));
+    TRY(timer.start());
+    TRY(s.keys.alloc(pool, 2 * P * 8, st));
+    TRY(s.vals.alloc(pool, 2 * P, st));
+    TRY(s.uscan.alloc(pool, (P + 1) * 8, st));
     uint64_t* keys = s.keys.as<uint64_t>();
     uint8_t* vals = s.vals.as<uint8_t>();
-    hipLaunchKernelGGL(k_ed_emit, grid(C), dim3(256), 0, st, s.mask.as<uint32_t>(), s.kbase.as<uint64_t>(),
+    hipLaunchKernelGGL(k_ed_emit, seed_grid(x, C), dim3(256), 0, st, s.mask.as<uint32_t>(), s.kbase.as<uint64_t>(),
                        s.dists.as<ulonglong2>(), s.pscan.as<uint64_t>(), C, keys, vals);
     HIP_TRY(hipGetLastError());
     const uint32_t kbits = std::min<uint32_t>(64, s.ebits + (nq > 1 ? ed_bits(nq - 1) : 0));
@@ -368,25 +315,18 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
         size_t tbytes = 0;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
         MmPoolBuf tmp;
-        TRY(tmp.alloc(s.pool, tbytes, st));
+        TRY(tmp.alloc(pool, tbytes, st));
         HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
     }
     s.skeys = kdb.current();
     s.svals = vdb.current();
-    TRY(mm_scan(s.pool, st,
+    TRY(mm_scan(pool, st,
                 rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), EdFirst{s.skeys, P}),
                 s.uscan.as<uint64_t>(), P + 1));
-    hipLaunchKernelGGL(k_ed_offsets, grid(nq + 1), dim3(256), 0, st, s.skeys, s.uscan.as<uint64_t>(), P, nq, s.ebits,
-                       out_off, out_total);
+    hipLaunchKernelGGL(k_ed_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, s.skeys, s.uscan.as<uint64_t>(), P, nq,
+                       s.ebits, out_off, out_total);
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        ed_last_dedup_ms = ms;
-    }
-    return 0;
+    return timer.stop(&ed_last_dedup_ms);
 }
 
 static int ed_scatter(const sas_index* x, EdState& s, void* out_end, uint8_t* out_dist, uint64_t capacity,
@@ -408,25 +348,15 @@ static int edit_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, 
                      uint64_t* out_off, void* out_end, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
                      uint64_t* out_total, void* stream, uint32_t flags) {
     const std::string w(fn);
-    if (!x) SAS_FAIL(EINVAL, w + ": null index");
-    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
-    if (x->tag_lines || x->sa_w == 8)
-        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
-    if (x->rank_lo != 0 || x->sa_n != x->n)
-        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
-    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
+    TRY(seed_index_checks(w, x, k, flags, stream));
     const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
     if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_end) ||
         (!dev && !out_total))
         SAS_FAIL(EINVAL, w + ": null argument");
-    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
-        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
     // the (query, end) sort key: the bits of an end in [0, n] above those of a query number
     if (ed_bits(x->n) + (nq > 1 ? ed_bits(nq - 1) : 0) > 64)
         SAS_FAIL(EINVAL, w + ": " + std::to_string(nq) + " queries on a text of " + std::to_string(x->n) +
                              " chars do not fit the 64-bit (query, end) sort key: split the batch");
-    // the range search's own requirements (its error is passed on)
-    TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq == 0) {
@@ -446,28 +376,16 @@ static int edit_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, 
         return ed_scatter(x, s, out_end, out_dist, capacity, st, flags);
     }
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
-        span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
-    }
-    DevBuf dq, dqoff, dqlen, doff, dfl, dend, ddist;
-    TRY(dq.alloc(span + 64, "edit queries"));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(dqoff.alloc(nq * 8, "edit offsets"));
-        TRY(dqlen.alloc(nq * 4, "edit lengths"));
-        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-    }
-    TRY(doff.alloc((nq + 1) * 8, "edit result offsets"));
-    TRY(dfl.alloc(nq, "edit query flags"));
-    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
-    TRY(ed_prepare(x, Q, k, max_seed_hits, doff.as<uint64_t>(), dfl.as<uint8_t>(), nullptr, st, flags | SAS_VALIDATE,
-                   s));
-    HIP_TRY(hipMemcpyAsync(out_off, doff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (out_qflags) HIP_TRY(hipMemcpyAsync(out_qflags, dfl.p, nq, hipMemcpyDeviceToHost, st));
+    HostQueries hq;
+    HostOutputs ho;
+    MmQueries Q;
+    TRY(hq.stage("edit", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
+    uint64_t* doff;
+    uint8_t* dfl;
+    TRY(ho.twin(out_off, (nq + 1) * 8, "edit result offsets", &doff));
+    TRY(ho.twin(out_qflags, nq, "edit query flags", &dfl));
+    TRY(ed_prepare(x, Q, k, max_seed_hits, doff, dfl, nullptr, st, flags | SAS_VALIDATE, s));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t total = out_off[nq];
     *out_total = total;
@@ -475,12 +393,12 @@ static int edit_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, 
         SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " ends, capacity " + std::to_string(capacity) +
                              " (size out_end from *out_total and call again)");
     if (total == 0) return 0;
-    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8;
-    TRY(dend.alloc(total * esz, "edit ends"));
-    if (out_dist) TRY(ddist.alloc(total, "edit distances"));
-    TRY(ed_scatter(x, s, dend.p, out_dist ? ddist.as<uint8_t>() : nullptr, total, st, flags));
-    HIP_TRY(hipMemcpyAsync(out_end, dend.p, total * esz, hipMemcpyDeviceToHost, st));
-    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, ddist.p, total, hipMemcpyDeviceToHost, st));
+    void* dend;
+    uint8_t* ddist;
+    TRY(ho.twin(out_end, total * ((flags & SAS_LOCATE_U32) ? 4 : 8), "edit ends", &dend));
+    TRY(ho.twin(out_dist, total, "edit distances", &ddist));
+    TRY(ed_scatter(x, s, dend, ddist, total, st, flags));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -28,6 +28,7 @@
 // SAS_BUILD_TAG_LINES has no SA array: a rank is looked up through tl_sa_at (common.hpp), a
 // binary search over the buckets' first ranks per element.  That path is correct, not tuned.
 #include "build_util.hpp"
+#include "csr_tile.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -68,17 +69,6 @@ __global__ void k_locate_count(const uint64_t* __restrict__ lo, const uint64_t* 
     }
 }
 
-// the last k in [0, nq] with off[k] <= v (off[0] = 0; nq when v >= the total)
-__device__ __forceinline__ uint64_t locate_query_of(const uint64_t* __restrict__ off, uint64_t nq, uint64_t v) {
-    uint64_t l = 0, h = nq + 1;
-    while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if (off[mid] <= v) l = mid + 1;
-        else h = mid;
-    }
-    return l ? l - 1 : 0;
-}
-
 // What a tile needs before it touches the SA, one 32-B record per tile boundary t in
 // [0, ntiles]: the query q of output element t * LOC_T, off[q], off[q + 1] and lo[q] (zeros
 // past the total).  The fill reads its tile's record in one request and the next tile's
@@ -100,7 +90,7 @@ __device__ __forceinline__ LocTile locate_tile_of(const uint64_t* __restrict__ l
 
 __global__ void k_locate_tiles(const uint64_t* __restrict__ lo, const uint64_t* __restrict__ off, uint64_t nq,
                                uint64_t ntiles, LocTile* __restrict__ tiles) {
-    GRID_STRIDE(t, ntiles + 1) tiles[t] = locate_tile_of(lo, off, nq, locate_query_of(off, nq, t * (uint64_t)LOC_T));
+    GRID_STRIDE(t, ntiles + 1) tiles[t] = locate_tile_of(lo, off, nq, csr_owner_of(off, nq, t * (uint64_t)LOC_T));
 }
 
 template <class SA, bool U32>
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_locate_fill(SA sa, uint64_t sa_n,
         if (tiles) {
             if (tile + gridDim.x < ntiles) nx = tiles[tile + gridDim.x];  // in flight during this tile's copy
         } else {
-            if (tid < 2) sh_q[tid] = locate_query_of(off, nq, t0 + (uint64_t)tid * LOC_T);
+            if (tid < 2) sh_q[tid] = csr_owner_of(off, nq, t0 + (uint64_t)tid * LOC_T);
             __syncthreads();
             r = locate_tile_of(lo, off, nq, sh_q[0]);
             q1 = sh_q[1];

@@ -25,7 +25,7 @@
 //     pattern[i .. min(i + max_len, plen)) derived from i (no offset / length arrays);
 //   * the ranks [lo, hi) of q[0 .. len) are the existing range search's, run on the same bytes
 //     with qlen = out_len (for fixed / stats queries the kernel leaves their offsets in scratch).
-#include "build_util.hpp"
+#include "seed_verify.hpp"
 
 #include <type_traits>
 #include <vector>
@@ -266,15 +266,8 @@ static int match_impl(const char* fn, const sas_index* x, int mode, const uint8_
                       const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t* out_len, uint64_t* out_pos,
                       uint64_t* out_lo, uint64_t* out_hi, void* stream, uint32_t flags) {
     const std::string w(fn);
-    if (!x) SAS_FAIL(EINVAL, w + ": null index");
-    if (x->tag_lines || x->sa_w == 8)
-        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
-    if (x->rank_lo != 0 || x->sa_n != x->n)
-        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
-    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
-    const bool ranges = out_lo || out_hi;
-    // the range search's own requirements (its error is passed on)
-    if (ranges) TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
+    // no k and no SAS_LOCATE_U32 here; the range search is asked only when it will run
+    TRY(seed_index_checks(w, x, 0, flags & SAS_DEVICE_PTRS, stream, out_lo || out_hi));
     if (nq == 0) return 0;
     if (!qbytes || !out_len || (mode == MATCH_RAGGED && (!qoff || !qlen))) SAS_FAIL(EINVAL, w + ": null argument");
     HIP_TRY(hipSetDevice(x->device));
@@ -282,40 +275,24 @@ static int match_impl(const char* fn, const sas_index* x, int mode, const uint8_
     if (flags & SAS_DEVICE_PTRS)
         return match_device(fn, x, mode, qbytes, qoff, qlen, m, nq, mode == MATCH_RAGGED ? 0 : (m ? m : 1),
                             (flags & SAS_VALIDATE) != 0, out_len, out_pos, out_lo, out_hi, st, flags);
-    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    uint64_t span = mode == MATCH_FIXED ? nq * (uint64_t)m : nq, maxlen = m;
-    if (mode == MATCH_RAGGED) {
-        span = maxlen = 0;
-        for (uint64_t k = 0; k < nq; k++) {
-            const uint64_t e = qoff[k] + qlen[k];
-            if (e > span) span = e;
-            if (qlen[k] > maxlen) maxlen = qlen[k];
-        }
-    }
-    DevBuf dq, doff, dqlen, dlen, dpos, dlo, dhi;
-    TRY(dq.alloc(span + 64, "match queries"));
+    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated).
+    // The pattern of MATCH_STATS is copied as plen queries of one char
+    const bool ragged = mode == MATCH_RAGGED;
+    const uint64_t maxlen = ragged ? *std::max_element(qlen, qlen + nq) : m;
+    HostQueries hq;
+    HostOutputs ho;
+    MmQueries Q;
+    TRY(hq.stage("match", qbytes, ragged, qoff, qlen, mode == MATCH_STATS ? 1 : m, nq, st, &Q));
+    uint32_t* dlen;
+    uint64_t *dpos, *dlo, *dhi;
+    TRY(ho.twin(out_len, nq * 4, "match lengths out", &dlen));
+    TRY(ho.twin(out_pos, nq * 8, "match positions", &dpos));
+    TRY(ho.twin(out_lo, nq * 8, "match range starts", &dlo));
+    TRY(ho.twin(out_hi, nq * 8, "match range ends", &dhi));
+    TRY(match_device(fn, x, mode, Q.qbytes, Q.qoff, ragged ? Q.qlen : nullptr, m, nq, maxlen ? maxlen : 1, true, dlen,
+                     dpos, dlo, dhi, st, flags | SAS_DEVICE_PTRS));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (mode == MATCH_RAGGED) {
-        TRY(doff.alloc(nq * 8, "match offsets"));
-        TRY(dqlen.alloc(nq * 4, "match lengths"));
-        HIP_TRY(hipMemcpy(doff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-    }
-    TRY(dlen.alloc(nq * 4, "match lengths out"));
-    if (out_pos) TRY(dpos.alloc(nq * 8, "match positions"));
-    if (out_lo) TRY(dlo.alloc(nq * 8, "match range starts"));
-    if (out_hi) TRY(dhi.alloc(nq * 8, "match range ends"));
-    TRY(match_device(fn, x, mode, dq.as<uint8_t>(), mode == MATCH_RAGGED ? doff.as<uint64_t>() : nullptr,
-                     mode == MATCH_RAGGED ? dqlen.as<uint32_t>() : nullptr, m, nq, maxlen ? maxlen : 1, true,
-                     dlen.as<uint32_t>(), out_pos ? dpos.as<uint64_t>() : nullptr,
-                     out_lo ? dlo.as<uint64_t>() : nullptr, out_hi ? dhi.as<uint64_t>() : nullptr, st,
-                     flags | SAS_DEVICE_PTRS));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(out_len, dlen.p, nq * 4, hipMemcpyDeviceToHost));
-    if (out_pos) HIP_TRY(hipMemcpy(out_pos, dpos.p, nq * 8, hipMemcpyDeviceToHost));
-    if (out_lo) HIP_TRY(hipMemcpy(out_lo, dlo.p, nq * 8, hipMemcpyDeviceToHost));
-    if (out_hi) HIP_TRY(hipMemcpy(out_hi, dhi.p, nq * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -9,12 +9,13 @@
 //   1. k_mm_pieces     offsets and lengths of the nq (k + 1) pieces (ragged queries that overlap
 //                      in the caller's bytes, which the range search takes);
 //   2. sas_search_range over all pieces: their SA rank ranges;
-//   3. k_mm_gate       empties the range of every piece that occurs more than max_seed_hits
+//   3. k_seed_gate     empties the range of every piece that occurs more than max_seed_hits
 //                      times (a skipped seed) and of every piece of a query with m <= k; writes
 //                      the per-query flags and a per-query mask of skipped pieces;
 //   4. sas_locate_offsets on the gated ranges: the candidate offsets, one candidate per
-//                      occurrence of a piece; the host reads the candidate total C (the call's
-//                      one read-back: it sizes the candidate scratch and the grids);
+//                      occurrence of a piece (steps 1 to 4 are seed_candidates, seed_verify.hip,
+//                      shared with sas_edit.hip); the host reads the candidate total C (the
+//                      call's one read-back: it sizes the candidate scratch and the grids);
 //   5. k_mm_verify     output-centric over the C candidates as k_locate_fill is over positions:
 //                      a workgroup owns tiles of MM_T consecutive candidates, finds each one's
 //                      piece by bisecting the tile's slice of the candidate offsets in LDS, reads
@@ -47,28 +48,6 @@
 #include <vector>
 
 #define MM_REJECT 0xFFu
-
-// One thread per query: skipped seeds and short queries lose their ranges
-__global__ void k_mm_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint64_t* __restrict__ lo,
-                          uint64_t* __restrict__ hi, uint16_t* __restrict__ skip, uint8_t* __restrict__ qflags) {
-    GRID_STRIDE(q, Q.nq) {
-        const bool is_short = Q.len(q) < kp1;  // m <= k
-        uint32_t mask = 0, fl = is_short ? SAS_MM_SHORT : 0u;
-        for (uint32_t j = 0; j < kp1; j++) {
-            const uint64_t i = q * kp1 + j;
-            const uint64_t cnt = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
-            const bool over = !is_short && max_seed_hits && cnt > max_seed_hits;
-            if (over) fl |= SAS_MM_TRUNCATED;
-            if (over || is_short) {
-                mask |= 1u << j;
-                lo[i] = 0;
-                hi[i] = 0;
-            }
-        }
-        skip[q] = (uint16_t)mask;
-        qflags[q] = (uint8_t)fl;
-    }
-}
 
 // words of query q in the packed scratch: ceil(m / 32)
 __global__ void k_mm_wcount(MmQueries Q, uint64_t* __restrict__ woff) {
@@ -220,8 +199,8 @@ extern "C" double sas_locate_mismatch_verify_ms(uint64_t* candidates) {
 
 // Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
 struct MmState {
-    hipMemPool_t pool = nullptr;
-    MmPoolBuf poff, plen, lohi, coff, skip, qfl, woff, qw, verdict, cpos, scan;
+    SeedState seed;
+    MmPoolBuf woff, qw, verdict, cpos, scan;
     uint64_t C = 0;
 };
 
@@ -230,40 +209,22 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
                       uint8_t* out_qflags, uint64_t* out_total, hipStream_t st, uint32_t flags, MmState& s) {
     const uint32_t kp1 = k + 1;
     const uint64_t nq = Q.nq, np = nq * kp1;
-    TRY(sas_scratch_pool(x, &s.pool));
-    TRY(s.poff.alloc(s.pool, np * 8, st));
-    TRY(s.plen.alloc(s.pool, np * 4, st));
-    TRY(s.lohi.alloc(s.pool, np * 16, st));
-    TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
-    TRY(s.skip.alloc(s.pool, nq * 2, st));
-    if (!out_qflags) {
-        TRY(s.qfl.alloc(s.pool, nq, st));
-        out_qflags = s.qfl.as<uint8_t>();
-    }
-    uint64_t* lo = s.lohi.as<uint64_t>();
-    uint64_t* hi = lo + np;
-    const unsigned cap_grid = (unsigned)x->num_cus * 8;
-    const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
-    hipLaunchKernelGGL(k_mm_pieces, grid(np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(), s.plen.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
-    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, lo, hi, st, rflags));
-    hipLaunchKernelGGL(k_mm_gate, grid(nq), dim3(256), 0, st, Q, kp1, max_seed_hits, lo, hi, s.skip.as<uint16_t>(),
-                       out_qflags);
-    HIP_TRY(hipGetLastError());
-    TRY(sas_locate_offsets(x, lo, hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS));
+    // 1 to 4, with the mask of skipped pieces: no query is too long for the compare
+    TRY(seed_candidates(x, Q, k, max_seed_hits, 0xFFFFFFFFu, true, out_qflags, st, flags, s.seed));
+    hipMemPool_t pool = s.seed.pool;
+    uint64_t* coff = s.seed.coff.as<uint64_t>();
     // SAS_MM_QWORDS=packed: ceil(m / 32) words per query; for ragged queries their total is read
     // back together with the candidate total (one synchronisation)
     const bool pre = mm_prepacked();
     uint64_t words = nq * (((uint64_t)Q.m + 31) >> 5);
     if (pre) {
-        TRY(s.woff.alloc(s.pool, (nq + 1) * 8, st));
-        hipLaunchKernelGGL(k_mm_wcount, grid(nq + 1), dim3(256), 0, st, Q, s.woff.as<uint64_t>());
+        TRY(s.woff.alloc(pool, (nq + 1) * 8, st));
+        hipLaunchKernelGGL(k_mm_wcount, seed_grid(x, nq + 1), dim3(256), 0, st, Q, s.woff.as<uint64_t>());
         HIP_TRY(hipGetLastError());
-        TRY(mm_scan(s.pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
+        TRY(mm_scan(pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
         if (Q.qoff) HIP_TRY(hipMemcpyAsync(&words, s.woff.as<uint64_t>() + nq, 8, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipMemcpyAsync(&s.C, s.coff.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&s.C, coff + np, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t C = s.C;
     mm_last_candidates = C;
@@ -274,13 +235,14 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         return 0;
     }
     if (pre) {
-        TRY(s.qw.alloc(s.pool, words * 8, st));
-        hipLaunchKernelGGL(k_mm_prepack, grid(nq), dim3(256), 0, st, Q, s.woff.as<uint64_t>(), s.qw.as<uint64_t>());
+        TRY(s.qw.alloc(pool, words * 8, st));
+        hipLaunchKernelGGL(k_mm_prepack, seed_grid(x, nq), dim3(256), 0, st, Q, s.woff.as<uint64_t>(),
+                           s.qw.as<uint64_t>());
         HIP_TRY(hipGetLastError());
     }
-    TRY(s.verdict.alloc(s.pool, C + 1, st));
-    TRY(s.cpos.alloc(s.pool, C * 8, st));
-    TRY(s.scan.alloc(s.pool, (C + 1) * 8, st));
+    TRY(s.verdict.alloc(pool, C + 1, st));
+    TRY(s.cpos.alloc(pool, C * 8, st));
+    TRY(s.scan.alloc(pool, (C + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(s.verdict.as<uint8_t>() + C, MM_REJECT, 1, st));
     MmArgs a{};
     a.tw = x->text_w;
@@ -288,11 +250,11 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     a.sa = x->sa;
     a.Q = Q;
     a.k = k;
-    a.lo = lo;
-    a.coff = s.coff.as<uint64_t>();
+    a.lo = s.seed.lo;
+    a.coff = coff;
     a.np = np;
     a.C = C;
-    a.skip = s.skip.as<uint16_t>();
+    a.skip = s.seed.skip.as<uint16_t>();
     a.woff = s.woff.as<uint64_t>();
     a.qw = s.qw.as<uint64_t>();
     a.verdict = s.verdict.as<uint8_t>();
@@ -300,13 +262,8 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     uint64_t blocks = (C + MM_T - 1) / MM_T;
     if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
     const dim3 vgrid((unsigned)tile_grid(blocks));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timing = mm_timing();
-    if (timing) {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-    }
+    SeedTimer timer(mm_timing(), st);
+    TRY(timer.start());
     if (x->sa_w == 5) {
         if (pre) hipLaunchKernelGGL((k_mm_verify<5, true>), vgrid, dim3(MM_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_mm_verify<5, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
@@ -315,19 +272,11 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         else hipLaunchKernelGGL((k_mm_verify<4, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
     }
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        mm_last_verify_ms = ms;
-    }
-    TRY(mm_scan(s.pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
+    TRY(timer.stop(&mm_last_verify_ms));
+    TRY(mm_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
                 s.scan.as<uint64_t>(), C + 1));
-    hipLaunchKernelGGL(k_mm_offsets, grid(nq + 1), dim3(256), 0, st, s.coff.as<uint64_t>(), s.scan.as<uint64_t>(), nq,
-                       kp1, out_off, out_total);
+    hipLaunchKernelGGL(k_mm_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, coff, s.scan.as<uint64_t>(), nq, kp1,
+                       out_off, out_total);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -351,21 +300,11 @@ static int mismatch_impl(const char* fn, const sas_index* x, const uint8_t* qbyt
                          uint64_t* out_off, void* out_pos, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
                          uint64_t* out_total, void* stream, uint32_t flags) {
     const std::string w(fn);
-    if (!x) SAS_FAIL(EINVAL, w + ": null index");
-    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
-    if (x->tag_lines || x->sa_w == 8)
-        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
-    if (x->rank_lo != 0 || x->sa_n != x->n)
-        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
-    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
-    // the range search's own requirements (its error is passed on)
-    TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
+    TRY(seed_index_checks(w, x, k, flags, stream));
     const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
     if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_pos) ||
         (!dev && !out_total))
         SAS_FAIL(EINVAL, w + ": null argument");
-    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
-        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (nq == 0) {
@@ -385,28 +324,16 @@ static int mismatch_impl(const char* fn, const sas_index* x, const uint8_t* qbyt
         return mm_scatter(x, s, out_pos, out_dist, capacity, st, flags);
     }
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
-        span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
-    }
-    DevBuf dq, dqoff, dqlen, doff, dfl, dtot, dpos, ddist;
-    TRY(dq.alloc(span + 64, "mismatch queries"));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(dqoff.alloc(nq * 8, "mismatch offsets"));
-        TRY(dqlen.alloc(nq * 4, "mismatch lengths"));
-        HIP_TRY(hipMemcpy(dqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-    }
-    TRY(doff.alloc((nq + 1) * 8, "mismatch result offsets"));
-    TRY(dfl.alloc(nq, "mismatch query flags"));
-    const MmQueries Q{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
-    TRY(mm_prepare(x, Q, k, max_seed_hits, doff.as<uint64_t>(), dfl.as<uint8_t>(), nullptr, st, flags | SAS_VALIDATE,
-                   s));
-    HIP_TRY(hipMemcpyAsync(out_off, doff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (out_qflags) HIP_TRY(hipMemcpyAsync(out_qflags, dfl.p, nq, hipMemcpyDeviceToHost, st));
+    HostQueries hq;
+    HostOutputs ho;
+    MmQueries Q;
+    TRY(hq.stage("mismatch", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
+    uint64_t* doff;
+    uint8_t* dfl;
+    TRY(ho.twin(out_off, (nq + 1) * 8, "mismatch result offsets", &doff));
+    TRY(ho.twin(out_qflags, nq, "mismatch query flags", &dfl));
+    TRY(mm_prepare(x, Q, k, max_seed_hits, doff, dfl, nullptr, st, flags | SAS_VALIDATE, s));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t total = out_off[nq];
     *out_total = total;
@@ -414,12 +341,12 @@ static int mismatch_impl(const char* fn, const sas_index* x, const uint8_t* qbyt
         SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " positions, capacity " + std::to_string(capacity) +
                              " (size out_pos from *out_total and call again)");
     if (total == 0) return 0;
-    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8;
-    TRY(dpos.alloc(total * esz, "mismatch positions"));
-    if (out_dist) TRY(ddist.alloc(total, "mismatch distances"));
-    TRY(mm_scatter(x, s, dpos.p, out_dist ? ddist.as<uint8_t>() : nullptr, total, st, flags));
-    HIP_TRY(hipMemcpyAsync(out_pos, dpos.p, total * esz, hipMemcpyDeviceToHost, st));
-    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, ddist.p, total, hipMemcpyDeviceToHost, st));
+    void* dpos;
+    uint8_t* ddist;
+    TRY(ho.twin(out_pos, total * ((flags & SAS_LOCATE_U32) ? 4 : 8), "mismatch positions", &dpos));
+    TRY(ho.twin(out_dist, total, "mismatch distances", &ddist));
+    TRY(mm_scatter(x, s, dpos, ddist, total, st, flags));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -1,6 +1,7 @@
 // sas_rescue.hip -- paired-end mapping with mate rescue (sas.h: sas_map_pairs_rescue,
-// sas_map_pairs_rescue_fixed).  Steps 1..3 and the records are pair_path.hpp's, the code of
-// sas_map_pairs; between them, for the pairs that the join left without a proper candidate:
+// sas_map_pairs_rescue_fixed).  Steps 1..3 and the records are those of sas_map_pairs
+// (pair_path.hpp declares them, sas_pairs.hip defines them); between them, for the pairs that the
+// join left without a proper candidate:
 //
 //   3a. the anchors    every locus of an eligible pair (no proper candidate, at most max_anchors
 //                      loci over both mates and strands) whose partner's length takes part is an
@@ -26,6 +27,9 @@
 //                      combines them per pair with a 64-bit atomicMin and atomicAdd: integer min
 //                      and add only, so the result does not depend on the order of arrival.
 #include "pair_path.hpp"
+
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #ifndef RS_CHUNK
 #define RS_CHUNK SAS_RESCUE_CHUNK  // window ends per work item (DESIGN §5 has the sweep)
@@ -175,8 +179,6 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
     if (c.max_anchors && P) {  // without a proposal there is no locus and no anchor
         hipMemPool_t pool;
         TRY(sas_scratch_pool(x, &pool));
-        const unsigned cap_grid = (unsigned)x->num_cus * 8;
-        const auto grid = [&](uint64_t count) { return dim3(tile_grid(std::min(grid_for(count), cap_grid))); };
         // the rescue's slots and the anchor scratch, sized from P: anchors <= loci <= P
         TRY(rslots.alloc(pool, 2 * np * 8, st));
         HIP_TRY(hipMemsetAsync(rslots.p, 0xFF, np * 8, st));
@@ -201,7 +203,7 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
         // 3a. the anchors
         TRY(mm_scan(pool, st, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), an),
                     ascan.as<uint64_t>(), P + 1));
-        hipLaunchKernelGGL(k_rescue_anchors, grid(P), dim3(256), 0, st, an, ascan.as<uint64_t>(), P,
+        hipLaunchKernelGGL(k_rescue_anchors, seed_grid(x, P), dim3(256), 0, st, an, ascan.as<uint64_t>(), P,
                            aidx.as<uint64_t>());
         HIP_TRY(hipGetLastError());
         // 3b. the window scans
@@ -223,7 +225,7 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
         a.rcnt = rcnt;
         // the grid is capped and strides over the item count, which stays on the device
         const uint64_t upper = P * (uint64_t)a.cpa;
-        const dim3 rgrid(tile_grid(std::min(grid_for(upper, RS_BLOCK), cap_grid)));
+        const dim3 rgrid(tile_grid(std::min(grid_for(upper, RS_BLOCK), (unsigned)x->num_cus * 8)));
         if (B.qoff) hipLaunchKernelGGL(k_pair_rescue<0>, rgrid, dim3(RS_BLOCK), 0, st, a);
         else if (B.m <= 64) hipLaunchKernelGGL(k_pair_rescue<1>, rgrid, dim3(RS_BLOCK), 0, st, a);
         else if (B.m <= 128) hipLaunchKernelGGL(k_pair_rescue<2>, rgrid, dim3(RS_BLOCK), 0, st, a);

@@ -1,0 +1,127 @@
+// seed_verify.hip -- the stages that every seed-and-verify call runs, defined once
+// (seed_verify.hpp declares them): the index preconditions, the seed stage up to the candidate
+// offsets, and the host-pointer path (queries in, outputs back).
+#include "seed_verify.hpp"
+
+static_assert(SAS_MM_TRUNCATED == SAS_ED_TRUNCATED && SAS_MM_SHORT == SAS_ED_SHORT,
+              "k_seed_gate writes one set of flag bits for sas_locate_mismatch and sas_locate_edit");
+
+int seed_index_checks(const std::string& w, const sas_index* x, uint32_t k, uint32_t flags, void* stream, bool probe) {
+    if (!x) SAS_FAIL(EINVAL, w + ": null index");
+    if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
+    if (x->tag_lines || x->sa_w == 8)
+        SAS_FAIL(ENOTSUP, w + ": a tagged index (SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES) is not served");
+    if (x->rank_lo != 0 || x->sa_n != x->n)
+        SAS_FAIL(ENOTSUP, w + ": needs a whole index (a shard or part holds only a rank range of the SA)");
+    if (!x->sa || (x->sa_w != 4 && x->sa_w != 5)) SAS_FAIL(ENOTSUP, w + ": needs a u32 or packed 40-bit SA array");
+    if ((flags & SAS_LOCATE_U32) && x->n >= (1ull << 32))
+        SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
+    // the range search's own requirements (its error is passed on)
+    if (probe) TRY(sas_search_range_fixed(x, nullptr, 1, 0, nullptr, nullptr, stream, flags & SAS_DEVICE_PTRS));
+    return 0;
+}
+
+__global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff, uint32_t* __restrict__ plen) {
+    GRID_STRIDE(i, Q.nq * kp1) {
+        const uint64_t q = i / kp1;
+        const uint32_t j = (uint32_t)(i - q * kp1), m = Q.len(q);
+        const uint32_t b0 = mm_piece_start(j, m, kp1), b1 = mm_piece_start(j + 1, m, kp1);
+        poff[i] = Q.off(q) + b0;
+        plen[i] = b1 - b0;
+    }
+}
+
+// One thread per query: skipped seeds, short queries (m <= k) and long ones (m > max_m) lose
+// their ranges
+__global__ void k_seed_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, uint32_t max_m,
+                            uint64_t* __restrict__ lo, uint64_t* __restrict__ hi, uint16_t* __restrict__ skip,
+                            uint8_t* __restrict__ qflags) {
+    GRID_STRIDE(q, Q.nq) {
+        const uint32_t m = Q.len(q);
+        uint32_t mask = 0, fl = m < kp1 ? SAS_ED_SHORT : (m > max_m ? SAS_ED_LONG : 0u);
+        const bool none = fl != 0;
+        for (uint32_t j = 0; j < kp1; j++) {
+            const uint64_t i = q * kp1 + j;
+            const uint64_t cnt = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
+            const bool over = !none && max_seed_hits && cnt > max_seed_hits;
+            if (over) fl |= SAS_ED_TRUNCATED;
+            if (over || none) {
+                mask |= 1u << j;
+                lo[i] = 0;
+                hi[i] = 0;
+            }
+        }
+        if (skip) skip[q] = (uint16_t)mask;
+        qflags[q] = (uint8_t)fl;
+    }
+}
+
+int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t max_m,
+                    bool skip_mask, uint8_t* qflags, hipStream_t st, uint32_t flags, SeedState& s) {
+    const uint32_t kp1 = k + 1;
+    const uint64_t nq = Q.nq, np = nq * kp1;
+    TRY(sas_scratch_pool(x, &s.pool));
+    TRY(s.poff.alloc(s.pool, np * 8, st));
+    TRY(s.plen.alloc(s.pool, np * 4, st));
+    TRY(s.lohi.alloc(s.pool, np * 16, st));
+    TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
+    if (skip_mask) TRY(s.skip.alloc(s.pool, nq * 2, st));
+    if (!qflags) {
+        TRY(s.qfl.alloc(s.pool, nq, st));
+        qflags = s.qfl.as<uint8_t>();
+    }
+    s.lo = s.lohi.as<uint64_t>();
+    s.hi = s.lo + np;
+    hipLaunchKernelGGL(k_mm_pieces, seed_grid(x, np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(),
+                       s.plen.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
+    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, s.lo, s.hi, st, rflags));
+    hipLaunchKernelGGL(k_seed_gate, seed_grid(x, nq), dim3(256), 0, st, Q, kp1, max_seed_hits, max_m, s.lo, s.hi,
+                       s.skip.as<uint16_t>(), qflags);
+    HIP_TRY(hipGetLastError());
+    return sas_locate_offsets(x, s.lo, s.hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS);
+}
+
+int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& what) {
+    TRY(d.alloc(bytes, what.c_str()));
+    if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int HostQueries::stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
+                       const uint32_t* qlen, uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q) {
+    const std::string l(label);
+    uint64_t span = nq * (uint64_t)m;
+    if (ragged) {
+        span = 0;
+        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
+    }
+    TRY(dq.alloc(span + 64, (l + " queries").c_str()));  // the packers read whole words past the end
+    HIP_TRY(hipStreamSynchronize(st));
+    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
+    if (ragged) {
+        TRY(host_copy_in(dqoff, qoff, nq * 8, l + " query offsets"));
+        TRY(host_copy_in(dqlen, qlen, nq * 4, l + " query lengths"));
+    }
+    *Q = MmQueries{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
+    return 0;
+}
+
+int HostOutputs::twin_bytes(void* h, size_t nbytes, const char* what, void** d) {
+    *d = nullptr;
+    if (!h) return 0;
+    if (count == MAX) SAS_FAIL(EINVAL, std::string("HostOutputs: more than ") + std::to_string(MAX) + " outputs");
+    TRY(dev[count].alloc(nbytes, what));
+    host[count] = h;
+    bytes[count] = nbytes;
+    *d = dev[count++].p;
+    return 0;
+}
+
+int HostOutputs::copy_back(hipStream_t st) {
+    for (; copied < count; copied++)
+        if (bytes[copied])
+            HIP_TRY(hipMemcpyAsync(host[copied], dev[copied].p, bytes[copied], hipMemcpyDeviceToHost, st));
+    return 0;
+}

@@ -1,12 +1,23 @@
 // seed_verify.hpp -- what the seed-and-verify calls share (sas_mismatch.hip: Hamming distance,
-// sas_edit.hip: edit distance): the query batch as the kernels see it, the cut of a query into
-// k + 1 pieces, the output-centric tiling of the candidates (one candidate = one occurrence of
-// one piece) and of the elements of a CSR list (sas_align.hip: alignments, sas_map.hip: the bytes
-// of a ragged batch), stream-ordered scratch and a scan helper.
+// sas_edit.hip: edit distance, and the calls built on them: sas_align.hip, sas_map.hip,
+// sas_pairs.hip, sas_rescue.hip; sas_match.hip takes the host-side helpers):
+//
+//   * device code that the kernels of those files inline: the query batch as the kernels see it,
+//     the cut of a query into k + 1 pieces, and the output-centric tiling (csr_tile.hpp) of the
+//     candidates (one candidate = one occurrence of one piece) and of the elements of a CSR list
+//     (sas_align.hip: alignments, sas_map.hip: the bytes of a ragged batch);
+//   * stream-ordered scratch, a scan helper, the grid of the helper kernels and an event pair
+//     for the *_TIMING knobs;
+//   * declared here and defined once in seed_verify.hip: the index preconditions
+//     (seed_index_checks), the seed stage up to the candidate offsets (seed_candidates) and the
+//     host-pointer path of every call (HostQueries, HostOutputs).
 #pragma once
 #include "build_util.hpp"
+#include "csr_tile.hpp"
 
 #include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
 
 #define MM_BLOCK 256
 #define MM_T 2048          // candidates per tile
@@ -30,87 +41,25 @@ __device__ __forceinline__ uint32_t mm_piece_start(uint32_t j, uint32_t m, uint3
     return (uint32_t)(((uint64_t)j * m) / kp1);
 }
 
-[[maybe_unused]] static __global__ void k_mm_pieces(MmQueries Q, uint32_t kp1, uint64_t* __restrict__ poff,
-                                   uint32_t* __restrict__ plen) {
-    GRID_STRIDE(i, Q.nq * kp1) {
-        const uint64_t q = i / kp1;
-        const uint32_t j = (uint32_t)(i - q * kp1), m = Q.len(q);
-        const uint32_t b0 = mm_piece_start(j, m, kp1), b1 = mm_piece_start(j + 1, m, kp1);
-        poff[i] = Q.off(q) + b0;
-        plen[i] = b1 - b0;
-    }
-}
-
-// the last i in [0, np] with off[i] <= v (off[0] = 0): for v below the total a non-empty piece
-__device__ __forceinline__ uint64_t mm_piece_of(const uint64_t* __restrict__ off, uint64_t np, uint64_t v) {
-    uint64_t l = 0, h = np + 1;
-    while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if (off[mid] <= v) l = mid + 1;
-        else h = mid;
-    }
-    return l ? l - 1 : 0;
-}
-
 // The candidates [t0, t0 + n_el) of one tile (n_el <= MM_T), for the whole workgroup of MM_BLOCK
-// threads: element e = u MM_BLOCK + tid is occurrence c - coff[pi] of piece pi[u] (found by
-// bisecting the tile's slice of the candidate offsets, staged in `rel` when it fits) and lies
-// at text position pv[u] = SA[lo[pi] + c - coff[pi]]; ok[u] = 0 for an element past the tile or
-// one that fails the offsets' own bounds.  All SA reads of a thread are issued before the
-// first is used.  `rel` (MM_SLICE words) and `sh_p` (2 words) are LDS; the caller puts a
-// __syncthreads() between two tiles.
+// threads: element e = u MM_BLOCK + tid is occurrence c - coff[pi] of piece pi[u] (its owner in
+// the candidate offsets: csr_tile_owners) and lies at text position pv[u] = SA[lo[pi] + c -
+// coff[pi]]; ok[u] = 0 for an element past the tile, one that fails the offsets' own bounds or
+// one whose rank is no rank of the SA.  All SA reads of a thread are issued before the first is
+// used.  `rel` (MM_SLICE words) and `sh_p` (2 words) are LDS; the caller puts a __syncthreads()
+// between two tiles.
 template <class SA>
 __device__ __forceinline__ void mm_tile_candidates(const SA& sa, const uint64_t* __restrict__ coff,
                                                    const uint64_t* __restrict__ lo, uint64_t np, uint64_t n,
                                                    uint64_t t0, uint32_t n_el, uint32_t* rel, uint64_t* sh_p,
                                                    uint64_t (&pi)[MM_PER], uint64_t (&pv)[MM_PER],
                                                    uint32_t (&ok)[MM_PER]) {
-    const uint32_t tid = threadIdx.x;
-    // the pieces of the tile's first and last candidate (both non-empty)
-    if (tid < 2) sh_p[tid] = mm_piece_of(coff, np, tid ? t0 + n_el - 1 : t0);
-    __syncthreads();
-    const uint64_t p0 = sh_p[0];
-    uint64_t p1 = sh_p[1];
-    if (p1 < p0) p1 = p0;
-    if (p1 > np - 1) p1 = np - 1;
-    const uint64_t nps = p1 - p0 + 1;
-    const uint32_t staged = nps <= MM_SLICE ? 1u : 0u;
-    if (staged) {
-        for (uint32_t x = tid; x < (uint32_t)nps; x += MM_BLOCK) {
-            const uint64_t o = coff[p0 + x];
-            rel[x] = o <= t0 ? 0u : (o - t0 >= MM_T ? (uint32_t)MM_T : (uint32_t)(o - t0));
-        }
-        __syncthreads();
-    }
-    // element e of the tile belongs to the last piece x in [p0, p1] with coff[x] <= t0 + e
-    uint64_t rk[MM_PER];
-#pragma unroll
-    for (int u = 0; u < MM_PER; u++) {
-        const uint32_t e = u * MM_BLOCK + tid;
-        const uint64_t c = t0 + e;
-        ok[u] = e < n_el ? 1u : 0u;
-        pi[u] = rk[u] = 0;
-        if (ok[u]) {
-            uint64_t l = 1, h = nps;
-            if (staged) {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (rel[mid] <= e) l = mid + 1;
-                    else h = mid;
-                }
-            } else {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (coff[p0 + mid] <= c) l = mid + 1;
-                    else h = mid;
-                }
-            }
-            pi[u] = p0 + l - 1;
-            const uint64_t o = coff[pi[u]];
-            rk[u] = lo[pi[u]] + (c - o);
-            ok[u] = (o <= c && c < coff[pi[u] + 1] && rk[u] < n) ? 1u : 0u;
-        }
-    }
+    uint64_t rk[MM_PER] = {};
+    csr_tile_owners<MM_T, MM_SLICE, MM_BLOCK>(coff, np, t0, n_el, rel, sh_p, pi, ok,
+                                              [&](int u, uint64_t c, uint64_t p) {
+                                                  rk[u] = lo[p] + (c - coff[p]);
+                                                  return csr_in_bounds(coff, p, c) && rk[u] < n;
+                                              });
 #pragma unroll
     for (int u = 0; u < MM_PER; u++) pv[u] = ok[u] ? sa[rk[u]] : 0;
 }
@@ -121,55 +70,12 @@ __device__ __forceinline__ void mm_tile_candidates(const SA& sa, const uint64_t*
 #define AL_SLICE 2048       // query offsets of a tile staged in LDS (8 KiB)
 
 // The queries of the elements [t0, t0 + n_el) of one tile of a CSR list (n_el <= AL_T; off: its
-// nq + 1 offsets), for the whole workgroup of AL_BLOCK threads: element e = u AL_BLOCK + tid
-// belongs to the last query qi[u] with off[qi] <= t0 + e (bisecting the tile's slice of `off`,
-// staged in `rel` when it fits); ok[u] = 0 for an element past the tile or one that fails the
-// offsets' own bounds.  The caller puts a __syncthreads() between two tiles.
+// nq + 1 offsets), for the whole workgroup of AL_BLOCK threads: csr_tile_owners at the AL sizes
 __device__ __forceinline__ void al_tile_queries(const uint64_t* __restrict__ off, uint64_t nq, uint64_t t0,
                                                 uint32_t n_el, uint32_t* rel, uint64_t* sh_p, uint64_t (&qi)[AL_PER],
                                                 uint32_t (&ok)[AL_PER]) {
-    const uint32_t tid = threadIdx.x;
-    // the queries of the tile's first and last element (both non-empty)
-    if (tid < 2) sh_p[tid] = mm_piece_of(off, nq, tid ? t0 + n_el - 1 : t0);
-    __syncthreads();
-    const uint64_t p0 = sh_p[0];
-    uint64_t p1 = sh_p[1];
-    if (p1 < p0) p1 = p0;
-    if (p1 > nq - 1) p1 = nq - 1;
-    const uint64_t nps = p1 - p0 + 1;
-    const uint32_t staged = nps <= AL_SLICE ? 1u : 0u;
-    if (staged) {
-        for (uint32_t x = tid; x < (uint32_t)nps; x += AL_BLOCK) {
-            const uint64_t o = off[p0 + x];
-            rel[x] = o <= t0 ? 0u : (o - t0 >= AL_T ? (uint32_t)AL_T : (uint32_t)(o - t0));
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < AL_PER; u++) {
-        const uint32_t e = u * AL_BLOCK + tid;
-        const uint64_t c = t0 + e;
-        ok[u] = e < n_el ? 1u : 0u;
-        qi[u] = 0;
-        if (ok[u]) {
-            uint64_t l = 1, h = nps;
-            if (staged) {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (rel[mid] <= e) l = mid + 1;
-                    else h = mid;
-                }
-            } else {
-                while (l < h) {
-                    const uint64_t mid = (l + h) >> 1;
-                    if (off[p0 + mid] <= c) l = mid + 1;
-                    else h = mid;
-                }
-            }
-            qi[u] = p0 + l - 1;
-            ok[u] = (off[qi[u]] <= c && c < off[qi[u] + 1]) ? 1u : 0u;
-        }
-    }
+    csr_tile_owners<AL_T, AL_SLICE, AL_BLOCK>(off, nq, t0, n_el, rel, sh_p, qi, ok,
+                                              [&](int, uint64_t c, uint64_t q) { return csr_in_bounds(off, q, c); });
 }
 
 struct MmPoolBuf {  // stream-ordered scratch from the index's pool
@@ -196,3 +102,94 @@ static int mm_scan(hipMemPool_t pool, hipStream_t st, In in, uint64_t* out, uint
                                     st));
     return 0;
 }
+
+// The grid of a helper kernel of 256 threads that strides over `count` elements: at most 8
+// workgroups per CU, and SAS_TILE_GRID's cap
+static inline dim3 seed_grid(const sas_index* x, uint64_t count) {
+    return dim3(tile_grid(std::min(grid_for(count), (unsigned)x->num_cus * 8)));
+}
+
+// The event pair of SAS_MM_TIMING / SAS_ED_TIMING: nothing happens unless `on`; the events are
+// destroyed on every way out.  stop() synchronises and gives the time since the last start()
+struct SeedTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st;
+    bool on;
+    SeedTimer(bool on_, hipStream_t st_) : st(st_), on(on_) {}
+    SeedTimer(const SeedTimer&) = delete;
+    ~SeedTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int start() {
+        if (!on) return 0;
+        if (!e0) HIP_TRY(hipEventCreate(&e0));
+        if (!e1) HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        return 0;
+    }
+    int stop(double* ms_out) {
+        if (!on) return 0;
+        float ms = 0;
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *ms_out = ms;
+        return 0;
+    }
+};
+
+// What every call of the family asks of its index, in this order: an index, k <= MM_MAX_K, no
+// tagged index, a whole index, a u32 or packed 40-bit SA, SAS_LOCATE_U32 only below 2^32 chars
+// and, with `probe`, the range search's own requirements (its error is passed on).  w: the
+// call's name, the head of every message
+int seed_index_checks(const std::string& w, const sas_index* x, uint32_t k, uint32_t flags, void* stream,
+                      bool probe = true);
+
+// Steps 1 to 4 of sas_mismatch.hip and sas_edit.hip, the scratch of which stays in the state:
+// the pieces, their gated SA ranges [lo, hi) and the candidate offsets coff (np + 1; the caller
+// reads the candidate total coff[np] back when it needs it)
+struct SeedState {
+    hipMemPool_t pool = nullptr;
+    MmPoolBuf poff, plen, lohi, coff, qfl, skip;
+    uint64_t* lo = nullptr;  // np each
+    uint64_t* hi = nullptr;
+};
+
+// All arrays on the device.  A query of more than max_m chars gets no seeds and SAS_ED_LONG;
+// skip_mask: s.skip gets, per query, a u16 whose bit j says that piece j is no seed; qflags (may
+// be null): the per-query flags, SAS_MM_* = SAS_ED_*.  No host read
+int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t max_m,
+                    bool skip_mask, uint8_t* qflags, hipStream_t st, uint32_t flags, SeedState& s);
+
+// src[0 .. bytes) of the host in a device buffer of its own (synchronous)
+int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& what);
+
+// The host-pointer path's way in: the queries of a call on the device.  The bytes copied are
+// those up to the largest qoff + qlen, not their sum: ragged queries may overlap
+struct HostQueries {
+    DevBuf dq, dqoff, dqlen;
+    // Waits for `st`, then copies (synchronous).  label: the call's word in "<label> queries"
+    int stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff, const uint32_t* qlen,
+              uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q);
+};
+
+// The host-pointer path's way out: the device twins of a call's host outputs.  twin() allocates
+// one for a host pointer that is not null and hands out the device pointer (null for null);
+// copy_back() queues the copies to the host of every twin made since the last copy_back()
+struct HostOutputs {
+    static const int MAX = 16;
+    DevBuf dev[MAX];
+    void* host[MAX];
+    size_t bytes[MAX];
+    int count = 0, copied = 0;
+    int twin_bytes(void* h, size_t nbytes, const char* what, void** d);
+    template <class T>
+    int twin(T* h, size_t nbytes, const char* what, T** d) {
+        void* p = nullptr;
+        TRY(twin_bytes(h, nbytes, what, &p));
+        *d = static_cast<T*>(p);
+        return 0;
+    }
+    int copy_back(hipStream_t st);
+};
