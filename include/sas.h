@@ -945,9 +945,83 @@ int sas_search_multi(const sas_multi* multi, const uint8_t* qbytes, const uint64
 
 /* Real-data inputs.
  * sas_read_fasta: read_fasta_file (sas/util.rs:144-169) -- records concatenated,
- * A/C/G/T/a/c/g/t -> 0..3, every other byte -> 0; FASTA and FASTQ, no gzip.
+ * A/C/G/T/a/c/g/t -> 0..3; FASTA and FASTQ, no gzip.  The text alone does not say where a
+ * record starts nor which chars were no base (they are stored as code 0):
+ * sas_read_fasta_layout below reads the same bytes together with the sequence layout that
+ * keeps approximate matches inside one record and out of the gaps.
  * out == NULL -> only *len is computed (size the buffer, then call again). */
 int sas_read_fasta(const char* path, uint8_t* out, uint64_t cap, uint64_t* len);
+
+/* The sequence layout: a side table on a built index that says where the sequences of the text
+ * start and which stretches of it are real bases.  It is set after the build and changes neither
+ * the text, the SA nor any exact lookup.
+ *   - sequences: seq_start[0 .. nseq] is non-decreasing with seq_start[0] = 0 and seq_start[nseq]
+ *     = n; sequence i is the text [seq_start[i], seq_start[i + 1]) and may be empty (FASTA has
+ *     empty records, and the ids stay aligned with the names).  The sequence of an end position
+ *     e >= 1 is the largest i with seq_start[i] < e.  nseq < 2^32 - 1;
+ *   - segments, the stretches of real bases: seg_lo[i] < seg_hi[i] <= seg_lo[i + 1], seg_hi[i] <= n,
+ *     and no seq_start value lies strictly inside (seg_lo[i], seg_hi[i]): a segment lies inside
+ *     one sequence.  nseg may be 0 (everything is masked).  A position in no segment is a gap.
+ *     The segment of an end e is the one with lo < e <= hi.
+ * sas_check_layout (host only, no device call) returns EINVAL on anything else, with a
+ * sas_last_error message that names the offending entry.  sas_set_layout (host pointers) calls it
+ * first, copies the three arrays to the device and synchronises the device before it swaps them
+ * in; nseq == 0 clears the layout.  THE CALLER MUST HAVE NO CALL IN FLIGHT ON THE INDEX when it
+ * sets or clears the layout: a set index is no longer immutable at that moment.  Any index may
+ * carry a layout, shards, parts and tagged indexes included (sas_align_edit and sas_translate
+ * serve them).  sas_get_layout is the query (sas_stats keeps its size): the counts, and with
+ * non-null arrays (nseq + 1, nseg and nseg entries) the values; nseq = 0: no layout.
+ *
+ * With a layout set, each segment is a text of its own for the approximate calls; with none they
+ * run exactly as before, and a layout of one sequence and one segment [0, n) gives the same bytes:
+ *   - sas_locate_mismatch*: an alignment [s, s + m) is reported only if it lies inside one segment;
+ *   - sas_locate_edit*: D_L(e) = min over s of ed(q, t[s .. e)) with [s, e) inside one segment,
+ *     undefined (nothing is reported) for an e in no segment; the unflagged answer is {e : D_L(e)
+ *     <= k}, the union over the segments of the no-layout answer on t[lo .. hi) as a text of its
+ *     own, shifted by lo.  The seed gate is unchanged (max_seed_hits counts the SA occurrences in
+ *     the whole text); a seed occurrence that is not inside one segment is no candidate; for a
+ *     SAS_ED_TRUNCATED query "some occurrence pv of a non-skipped piece" is restricted to the
+ *     occurrences in the segment of e;
+ *   - sas_align_edit*: w0 = max(lo of e's segment, e - m - k); an end in no segment gets the
+ *     "no alignment" record;
+ *   - sas_map_edit*: its reduction over the constrained ends of both strands; n_best and n_loci
+ *     keep their run definitions;
+ *   - sas_map_pairs*: the loci are those of the constrained answers, and a candidate is proper
+ *     only if both of its ends have the same sequence.  Sequence, not segment: mates legitimately
+ *     span a gap inside one scaffold;
+ *   - sas_map_pairs_rescue*: the window W of partner ends is intersected with the anchor's
+ *     sequence i, (seq_start[i], seq_start[i + 1]]; the scanned distance is D_L, so an end in no
+ *     segment is no candidate and breaks a run of candidate ends like any other end that is none;
+ *     the window's first end, a run head, is the first end of the intersected window;
+ *   - the exact calls (sas_search*, sas_search_range*, sas_locate*, sas_match*) are index lookups
+ *     and ignore the layout: filter their positions with sas_translate.
+ *
+ * sas_translate: text positions back to (sequence, offset).  For the interval [pos[i], pos[i] +
+ * span[i]) (span_or_null == NULL: every span is 1; a span of 0 counts as 1): out_seq[i] = the
+ * sequence id if the interval lies inside one segment, else SAS_SEQ_NONE; out_off[i] = pos[i] -
+ * seq_start[id], or pos[i] itself beside SAS_SEQ_NONE.  pos and out_off are u64, or u32 with
+ * SAS_LOCATE_U32 (as sas_locate* wrote them; EINVAL for n >= 2^32); span and out_seq are u32.
+ * With SAS_DEVICE_PTRS the call is asynchronous on `stream` and reads nothing back; with host
+ * pointers it is synchronous.  EINVAL for an index without a layout. */
+#define SAS_SEQ_NONE 0xFFFFFFFFu
+int sas_check_layout(uint64_t n, const uint64_t* seq_start, uint64_t nseq,
+                     const uint64_t* seg_lo, const uint64_t* seg_hi, uint64_t nseg);
+int sas_set_layout(sas_index* index, const uint64_t* seq_start, uint64_t nseq,
+                   const uint64_t* seg_lo, const uint64_t* seg_hi, uint64_t nseg);
+int sas_get_layout(const sas_index* index, uint64_t* nseq, uint64_t* nseg,
+                   uint64_t* seq_start, uint64_t* seg_lo, uint64_t* seg_hi);
+int sas_translate(const sas_index* index, const void* pos, const uint32_t* span_or_null, uint64_t count,
+                  uint32_t* out_seq, void* out_off, void* stream, uint32_t flags);
+/* sas_read_fasta_layout: the text of sas_read_fasta, byte for byte (an SA built from it stays
+ * valid), with its layout: one sequence per record, FASTA or FASTQ (seq_start gets nseq + 1
+ * entries; seq_cap counts entries), a segment per maximal run of ACGTacgt inside a record, and
+ * in `names` each header's first word, NUL-terminated, in record order.  Every array may be NULL:
+ * it is then not written, and *len, *nseq, *nseg and *names_len (may be NULL) are still set, so a
+ * call with all of them NULL sizes the buffers.  ENOMEM when a non-null array is too small. */
+int sas_read_fasta_layout(const char* path, uint8_t* out, uint64_t cap, uint64_t* len,
+                          uint64_t* seq_start, uint64_t seq_cap, uint64_t* nseq,
+                          uint64_t* seg_lo, uint64_t* seg_hi, uint64_t seg_cap, uint64_t* nseg,
+                          char* names, uint64_t names_cap, uint64_t* names_len);
 /* sas_kmer_keys: the --human u32 keys of sst/bin/bench.rs:58-76 for the S-tree:
  * out[j] = packed chars [j, j+k) & i32::MAX, j < min(n, limit+k-1) - (k-1),
  * out[0] = i32::MAX.  out == NULL -> only *count.  k in 1..16. */

@@ -122,6 +122,28 @@ class SaNaive {
         return s;
     }
 
+    /* the sequence layout (sas_set_layout): seq_start has one more entry than sequences, from 0
+     * to n; the segments [seg_lo[i], seg_hi[i]) are the real bases.  An empty seq_start clears
+     * it.  No call may be in flight on the index */
+    void set_layout(const std::vector<uint64_t>& seq_start, const std::vector<uint64_t>& seg_lo = {},
+                    const std::vector<uint64_t>& seg_hi = {}) {
+        if (seg_lo.size() != seg_hi.size()) throw std::invalid_argument("set_layout: seg_lo and seg_hi differ in length");
+        if (seq_start.size() == 1) throw std::invalid_argument("set_layout: seq_start needs at least two entries");
+        check(sas_set_layout(h_, seq_start.data(), seq_start.empty() ? 0 : seq_start.size() - 1, seg_lo.data(),
+                             seg_hi.data(), seg_lo.size()));
+    }
+    /* (sequence id, offset) of each interval [pos[i], pos[i] + span[i]) (no spans: 1 each):
+     * SAS_SEQ_NONE and pos[i] itself unless the interval lies inside one segment (sas_translate) */
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> translate(const std::vector<uint64_t>& pos,
+                                                                     const std::vector<uint32_t>& span = {}) const {
+        if (!span.empty() && span.size() != pos.size()) throw std::invalid_argument("translate: one span per position");
+        std::vector<uint32_t> seq(pos.size());
+        std::vector<uint64_t> off(pos.size());
+        check(sas_translate(h_, pos.data(), span.empty() ? nullptr : span.data(), pos.size(), seq.data(), off.data(),
+                            nullptr, 0));
+        return {std::move(seq), std::move(off)};
+    }
+
     /* sa[rank] (SaNaive::suffix_at's position, sas/sa_search.rs:79-81) */
     uint64_t sa(uint64_t rank) const {
         uint64_t v = 0;

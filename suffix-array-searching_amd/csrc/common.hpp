@@ -19,7 +19,9 @@
 #include <stdint.h>
 #include <errno.h>
 #include <string>
+#include <vector>
 
+#include "layout.hpp"
 #include "../../include/sas.h"
 #include "../../include/sst.h"
 
@@ -199,6 +201,12 @@ struct sas_index {
     uint64_t* text2 = nullptr;     // SAS_BUILD_TAG_LINES: the packed text again, 64 B off the
     void* text2_base = nullptr;    // 128-B line grid (text2 = text2_base + 64 B; tl_text)
     sas_stats stats = {};
+    // the sequence layout (sas_set_layout, sas_io.hip): one device allocation holding seq_start,
+    // seg_lo and seg_hi, which `lay` points into, and the host's copy of the same three arrays
+    // in that order for sas_get_layout.  lay.nseq == 0: no layout
+    LayoutView lay = {};
+    uint64_t* lay_dev = nullptr;
+    std::vector<uint64_t> lay_host;
     mutable StagePool* stage = nullptr;  // created by the first host-pointer search
     mutable hipMemPool_t route_pool = nullptr;  // stream-ordered scratch of sas_route_pack (first use)
 };

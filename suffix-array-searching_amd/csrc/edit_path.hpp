@@ -58,6 +58,15 @@ struct EdMyers {
         lw = (m - 1) >> 6;
         lb = (m - 1) & 63;
     }
+    // Back to the state before the first column, the query kept: what a lane does where a new
+    // text begins under its columns (a segment's lo, sas_rescue.hip); the caller sets score = m
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            Pv[w] = ~0ull;
+            Mv[w] = 0;
+        }
+    }
     // One column: the text char in the top two bits of tx.  Returns the change of the score,
     // the horizontal delta of row m - 1 (free start: 0 into row 0)
     __device__ __forceinline__ int64_t column(uint64_t tx) {

@@ -30,6 +30,10 @@
 //   3.                the walk from (0, s) to (m, e) reads one record word per query char and
 //                     writes the run-length encoded script.
 //
+// On an index with a sequence layout (template bool LAY, layout.hpp) one bisect finds the segment
+// of e: an end in none has no alignment, and step 2 scans j >= lo of that segment where it
+// scanned j >= 0, which is w0 = max(lo, e - m - k) of sas.h.
+//
 // Scratch is T x rows x word bytes, T <= num_cus AL_BPC AL_BLOCK, rows = m (fixed length) or
 // SAS_ED_MAX_M (ragged): bounded by the grid, not by the number of alignments.
 #include "seed_verify.hpp"
@@ -52,6 +56,7 @@ struct AlArgs {
     uint8_t* out_nruns;     // may be null
     uint16_t* out_runs;     // may be null; 2k + 1 slots per alignment
     void* scr;              // direction words, [row][thread of the grid]
+    LayoutView lay;         // LAY: the index's sequence layout
 };
 
 template <int KB> struct AlWord;
@@ -63,8 +68,11 @@ template <> struct AlWord<15> { typedef uint64_t type; };
 // One alignment: 1 <= m <= SAS_ED_MAX_M, e <= n.  scr: this thread's column of the direction
 // words, row r at scr[r T].  Returns the distance (SAS_AL_NONE_DIST: none) and sets *s_out and
 // *nruns_out; the runs go to `runs` (2k + 1 slots, when not null), the unused slots as 0.
+// jmin: the least start, 0 or with a layout the lo of e's segment.  R[i][j] depends on t[j .. e)
+// alone and a cell feeds no cell of a larger j, so cutting the starts is all that a segment asks
 template <int KB>
-__device__ __forceinline__ uint32_t al_one(const AlArgs& a, uint32_t m, uint64_t e, const uint8_t* __restrict__ qb,
+__device__ __forceinline__ uint32_t al_one(const AlArgs& a, uint32_t m, uint64_t e, int64_t jmin,
+                                           const uint8_t* __restrict__ qb,
                                            typename AlWord<KB>::type* __restrict__ scr, uint64_t T, uint64_t* s_out,
                                            uint32_t* nruns_out, uint16_t* __restrict__ runs) {
     typedef typename AlWord<KB>::type DT;
@@ -132,7 +140,7 @@ __device__ __forceinline__ uint32_t al_one(const AlArgs& a, uint32_t m, uint64_t
         const int64_t j0 = se - (int64_t)m - KB;  // cell x of row 0 is column j0 + x
 #pragma unroll
         for (int x = BW - 1; x >= 0; x--) {
-            if (j0 + x >= 0 && v[x] < d) {
+            if (j0 + x >= jmin && v[x] < d) {
                 d = v[x];
                 sx = x;
             }
@@ -182,7 +190,7 @@ __device__ __forceinline__ uint32_t al_one(const AlArgs& a, uint32_t m, uint64_t
     return d;
 }
 
-template <int KB, bool U32>
+template <int KB, bool U32, bool LAY>
 __global__ __launch_bounds__(AL_BLOCK) void k_al_align(AlArgs a) {
     typedef typename AlWord<KB>::type DT;
     __shared__ uint32_t rel[AL_SLICE];
@@ -212,8 +220,15 @@ __global__ __launch_bounds__(AL_BLOCK) void k_al_align(AlArgs a) {
             const uint64_t e = U32 ? (uint64_t)static_cast<const uint32_t*>(a.end)[al]
                                    : static_cast<const uint64_t*>(a.end)[al];
             const uint32_t m = ok[u] ? a.Q.len(qi[u]) : 0u;
-            if (m >= 1 && m <= SAS_ED_MAX_M && e <= a.n) {
-                d = al_one<KB>(a, m, e, a.Q.qbytes + a.Q.off(qi[u]), scr, T, &s, &nr, runs);
+            int64_t jmin = 0;
+            bool in_seg = true;
+            if (LAY && e <= a.n) {  // one bisect on e: an end in no segment has no alignment
+                const uint64_t g = layout_seg_of_end(a.lay, e);
+                in_seg = g != LAYOUT_NONE;
+                if (in_seg) jmin = (int64_t)a.lay.seg_lo[g];
+            }
+            if (m >= 1 && m <= SAS_ED_MAX_M && e <= a.n && in_seg) {
+                d = al_one<KB>(a, m, e, jmin, a.Q.qbytes + a.Q.off(qi[u]), scr, T, &s, &nr, runs);
             } else if (runs) {
                 for (uint32_t r = 0; r < stride; r++) runs[r] = 0;
             }
@@ -246,8 +261,13 @@ __global__ void k_al_validate(const uint8_t* __restrict__ qb, const uint64_t* __
 
 template <int KB>
 static void al_launch(dim3 grid, hipStream_t st, const AlArgs& a, bool u32) {
-    if (u32) hipLaunchKernelGGL((k_al_align<KB, true>), grid, dim3(AL_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_al_align<KB, false>), grid, dim3(AL_BLOCK), 0, st, a);
+    if (a.lay.nseq) {  // a kernel of its own: without a layout the parent's instructions run
+        if (u32) hipLaunchKernelGGL((k_al_align<KB, true, true>), grid, dim3(AL_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_al_align<KB, false, true>), grid, dim3(AL_BLOCK), 0, st, a);
+        return;
+    }
+    if (u32) hipLaunchKernelGGL((k_al_align<KB, true, false>), grid, dim3(AL_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_al_align<KB, false, false>), grid, dim3(AL_BLOCK), 0, st, a);
 }
 
 // All arrays on the device.  No host read unless `validate`
@@ -288,6 +308,7 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
     a.out_nruns = out_nruns;
     a.out_runs = out_runs;
     a.scr = scr.p;
+    a.lay = x->lay;
     const dim3 grid((unsigned)blocks);
     const bool u32 = (flags & SAS_LOCATE_U32) != 0;
     if (kb == 1) al_launch<1>(grid, st, a, u32);

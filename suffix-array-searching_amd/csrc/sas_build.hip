@@ -1195,7 +1195,7 @@ static void free_index(sas_index* x) {
     if (!x) return;
     void* ptrs[] = {x->text_w, x->sa, x->lcp, x->llcp, x->prefix, x->stree, x->rel, x->scratch,
                      x->sec_inner, x->sec_leaves, x->quad_inner, x->quad_leaves, x->tag_table, x->tag_lines, x->tag_ovf,
-                     x->tag_first, x->text2_base};
+                     x->tag_first, x->text2_base, x->lay_dev};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     sas_stage_pool_free(x->stage);
     if (x->route_pool) {  // its blocks were freed stream-ordered: drain before destroying

@@ -29,7 +29,18 @@
 //                      a column >= n.  A candidate stops once score - columns left > k (the
 //                      score falls by at most 1 per column: nothing later can be reported).
 //                      Output per candidate: a mask of the accepted ends (bit i: e = s0 + m - k
-//                      + i), their distances 4 bits each, and the sort key of bit 0;
+//                      + i), their distances 4 bits each, and the sort key of bit 0.
+//                      On an index with a sequence layout (template bool LAY, layout.hpp) one
+//                      bisect finds the segment [lo, hi) of the seed occurrence, a seed that
+//                      is not inside one segment is no candidate, and the window is cut to
+//                      [max(lo, s0 - 2k), min(hi, s0 + m + k)) where it was cut to 0 and n.  The
+//                      exactness argument carries over: the alignments inside the segment are
+//                      a subset of all, so one of cost <= k that ends in the candidate's
+//                      interval still starts at or after s0 - 2k, and the score, capped at
+//                      k + 1, is D_L(e) of sas.h whichever candidate of that segment computes
+//                      it.  An end at or before lo or past hi gets no column, so a candidate
+//                      proposes ends of its own segment only, which is what sas.h asks of a
+//                      SAS_ED_TRUNCATED query;
 //   6. de-duplication  the same end is proposed by several pieces and, in repeats, by several
 //                      occurrences: popcount of the masks, exclusive scan, the host reads the
 //                      proposal total P (the call's second read-back: it sizes the sort), k_ed_emit
@@ -63,16 +74,18 @@ struct EdArgs {
     uint32_t* mask;         // per candidate: bit i = the end s0 + m - k + i is accepted
     uint64_t* kbase;        // per candidate: the key of bit 0 (modulo 2^64: s0 + m - k may be < 0)
     ulonglong2* dists;      // per candidate: the distance of bit i in bits [4 i, 4 i + 4)
+    LayoutView lay;         // LAY: the index's sequence layout
 };
 
 // Candidate = an occurrence of piece i at text position pv.  NW words of 64 rows (m <= 64 NW)
+// [t_lo, t_hi): the text the window is cut to: [0, n), or with a layout the seed's segment
 template <int NW>
-__device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64_t s0,
+__device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64_t s0, int64_t t_lo, int64_t t_hi,
                                               const uint8_t* __restrict__ qb, uint32_t* mask_out, uint64_t* d0_out,
                                               uint64_t* d1_out) {
-    const int64_t k = (int64_t)a.k, n = (int64_t)a.n;
-    const int64_t w0 = s0 - 2 * k > 0 ? s0 - 2 * k : 0;             // the window's columns [w0, w1)
-    const int64_t w1 = s0 + m + k < n ? s0 + (int64_t)m + k : n;
+    const int64_t k = (int64_t)a.k;
+    const int64_t w0 = s0 - 2 * k > t_lo ? s0 - 2 * k : t_lo;       // the window's columns [w0, w1)
+    const int64_t w1 = s0 + m + k < t_hi ? s0 + (int64_t)m + k : t_hi;
     const int64_t e0 = s0 + (int64_t)m - k;                         // the end of bit 0
     uint32_t mask = 0;
     uint64_t d0 = 0, d1 = 0;
@@ -103,7 +116,7 @@ __device__ __forceinline__ void ed_verify_one(const EdArgs& a, uint32_t m, int64
 }
 
 // NW: 1, 2, 4 words of 64 rows for every query of the batch (fixed length), 0: by each query's m
-template <int W, int NW>
+template <int W, int NW, bool LAY>
 __global__ __launch_bounds__(MM_BLOCK) void k_ed_verify(EdArgs a) {
     __shared__ uint32_t rel[MM_SLICE];
     __shared__ uint64_t sh_p[2];
@@ -129,10 +142,22 @@ __global__ __launch_bounds__(MM_BLOCK) void k_ed_verify(EdArgs a) {
                     const int64_t s0 = (int64_t)pv[u] - (int64_t)mm_piece_start(j, m, kp1);
                     const uint8_t* qb = a.Q.qbytes + a.Q.off(q);
                     kb = (q << a.ebits) + (uint64_t)(s0 + (int64_t)m - (int64_t)a.k);
-                    if (m >= kp1 && m <= SAS_ED_MAX_M) {  // gated already: a guard for the word count
-                        if (NW == 1 || (NW == 0 && m <= 64)) ed_verify_one<1>(a, m, s0, qb, &mask, &d0, &d1);
-                        else if (NW == 2 || (NW == 0 && m <= 128)) ed_verify_one<2>(a, m, s0, qb, &mask, &d0, &d1);
-                        else ed_verify_one<4>(a, m, s0, qb, &mask, &d0, &d1);
+                    int64_t t_lo = 0, t_hi = (int64_t)a.n;
+                    bool seed_ok = true;
+                    if (LAY) {  // the seed occurrence [pv, pv + len) must lie inside one segment
+                        const uint64_t g = layout_seg_of_pos(a.lay, pv[u]);
+                        const uint32_t len = mm_piece_start(j + 1, m, kp1) - mm_piece_start(j, m, kp1);
+                        seed_ok = g != LAYOUT_NONE && a.lay.seg_hi[g] - pv[u] >= len;
+                        if (seed_ok) {
+                            t_lo = (int64_t)a.lay.seg_lo[g];
+                            t_hi = (int64_t)a.lay.seg_hi[g];
+                        }
+                    }
+                    if (seed_ok && m >= kp1 && m <= SAS_ED_MAX_M) {  // gated already: a guard for the word count
+                        if (NW == 1 || (NW == 0 && m <= 64)) ed_verify_one<1>(a, m, s0, t_lo, t_hi, qb, &mask, &d0, &d1);
+                        else if (NW == 2 || (NW == 0 && m <= 128))
+                            ed_verify_one<2>(a, m, s0, t_lo, t_hi, qb, &mask, &d0, &d1);
+                        else ed_verify_one<4>(a, m, s0, t_lo, t_hi, qb, &mask, &d0, &d1);
                     }
                 }
                 a.mask[t0 + e] = mask;
@@ -231,10 +256,16 @@ extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
     return ed_last_dedup_ms;
 }
 
+// a kernel of its own for an index with a layout: without one the parent's instructions run
 template <int NW>
 static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, const EdArgs& a) {
-    if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW>), grid, dim3(MM_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_ed_verify<4, NW>), grid, dim3(MM_BLOCK), 0, st, a);
+    if (x->lay.nseq) {
+        if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_ed_verify<4, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
+    } else {
+        if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_ed_verify<4, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
+    }
 }
 
 // All arrays on the device (out_total may be null).  Two host reads: the candidate total and
@@ -279,6 +310,7 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     a.mask = s.mask.as<uint32_t>();
     a.kbase = s.kbase.as<uint64_t>();
     a.dists = s.dists.as<ulonglong2>();
+    a.lay = x->lay;
     uint64_t blocks = (C + MM_T - 1) / MM_T;
     if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
     const dim3 vgrid((unsigned)tile_grid(blocks));

@@ -20,7 +20,9 @@
 //                      a workgroup owns tiles of MM_T consecutive candidates, finds each one's
 //                      piece by bisecting the tile's slice of the candidate offsets in LDS, reads
 //                      SA[lo + i] and derives the alignment s = SA - b_j.  Alignments that leave
-//                      the text are rejected before any text read.  q and t[s .. s + m) are
+//                      the text are rejected before any text read, and on an index with a
+//                      sequence layout (template bool LAY, layout.hpp) those that do not lie
+//                      inside one segment: one bisect per candidate.  q and t[s .. s + m) are
 //                      compared 32 chars a step (text_chars32, XOR, popcount of the 2-bit
 //                      differences; the last word masked to m), stopping once the distance
 //                      exceeds k.  The mismatch bits of each step are also tested against the
@@ -78,12 +80,13 @@ struct MmArgs {
     const uint64_t* woff;   // PRE: first packed word per query
     const uint64_t* qw;     // PRE: packed query words
     uint8_t* verdict;       // per candidate: distance, or MM_REJECT
+    LayoutView lay;         // LAY: the index's sequence layout
     uint64_t* cpos;         // per accepted candidate: the alignment
 };
 
 // Candidate `c` = occurrence `rank` of piece i at text position pv: the verdict for the
 // alignment s = pv - b_j
-template <bool PRE>
+template <bool PRE, bool LAY>
 __device__ __forceinline__ uint32_t mm_verify_one(const MmArgs& a, uint64_t i, uint64_t pv, uint64_t* s_out) {
     const uint32_t kp1 = a.k + 1;
     const uint64_t q = i / kp1;
@@ -91,6 +94,10 @@ __device__ __forceinline__ uint32_t mm_verify_one(const MmArgs& a, uint64_t i, u
     const uint32_t bj = mm_piece_start(j, m, kp1);
     if (pv < bj || pv - bj + m > a.n) return MM_REJECT;  // leaves the text: no text read
     const uint64_t s = pv - bj;
+    if (LAY) {  // the alignment [s, s + m) must lie inside one segment: that of its first char
+        const uint64_t g = layout_seg_of_pos(a.lay, s);
+        if (g == LAYOUT_NONE || a.lay.seg_hi[g] - s < m) return MM_REJECT;
+    }
     *s_out = s;
     const uint32_t skipm = a.skip[q];
     const uint8_t* qb = PRE ? nullptr : a.Q.qbytes + a.Q.off(q);
@@ -119,7 +126,7 @@ __device__ __forceinline__ uint32_t mm_verify_one(const MmArgs& a, uint64_t i, u
     return dist;
 }
 
-template <int W, bool PRE>
+template <int W, bool PRE, bool LAY>
 __global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
     __shared__ uint32_t rel[MM_SLICE];
     __shared__ uint64_t sh_p[2];
@@ -138,12 +145,23 @@ __global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
             const uint32_t e = u * MM_BLOCK + tid;
             if (e < n_el) {
                 uint64_t s = 0;
-                const uint32_t v = ok[u] ? mm_verify_one<PRE>(a, pi[u], pv[u], &s) : MM_REJECT;
+                const uint32_t v = ok[u] ? mm_verify_one<PRE, LAY>(a, pi[u], pv[u], &s) : MM_REJECT;
                 a.verdict[t0 + e] = (uint8_t)v;
                 if (v != MM_REJECT) a.cpos[t0 + e] = s;
             }
         }
         __syncthreads();  // rel and sh_p are rewritten by the next tile
+    }
+}
+
+template <bool LAY>
+static void mm_launch_verify(const sas_index* x, bool pre, dim3 grid, hipStream_t st, const MmArgs& a) {
+    if (x->sa_w == 5) {
+        if (pre) hipLaunchKernelGGL((k_mm_verify<5, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_mm_verify<5, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
+    } else {
+        if (pre) hipLaunchKernelGGL((k_mm_verify<4, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_mm_verify<4, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
     }
 }
 
@@ -264,13 +282,10 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     const dim3 vgrid((unsigned)tile_grid(blocks));
     SeedTimer timer(mm_timing(), st);
     TRY(timer.start());
-    if (x->sa_w == 5) {
-        if (pre) hipLaunchKernelGGL((k_mm_verify<5, true>), vgrid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mm_verify<5, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
-    } else {
-        if (pre) hipLaunchKernelGGL((k_mm_verify<4, true>), vgrid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mm_verify<4, false>), vgrid, dim3(MM_BLOCK), 0, st, a);
-    }
+    // a kernel of its own for an index with a layout: without one the parent's instructions run
+    a.lay = x->lay;
+    if (x->lay.nseq) mm_launch_verify<true>(x, pre, vgrid, st, a);
+    else mm_launch_verify<false>(x, pre, vgrid, st, a);
     HIP_TRY(hipGetLastError());
     TRY(timer.stop(&mm_last_verify_ms));
     TRY(mm_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),

@@ -197,6 +197,7 @@ struct PairJoin {
     uint64_t* pmin;         // per pair: the least pass-1 key (MAP_NONE before pass 1)
     uint64_t* pcnt;         // per pair: proper candidates (0 before pass 1)
     uint64_t* pbest;        // per pair: those at the least sum (0 before pass 2)
+    LayoutView lay;         // the index's sequence layout (nseq == 0: none)
 };
 
 template <int PASS>
@@ -239,8 +240,17 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_pair_join(PairJoin a) {
             }
             // the partner window: the reverse-strand loci of the other mate with lo <= e_y <= hi
             const uint64_t bv = (a.nfwd + (b ^ 1ull)) << a.ebits;
-            const uint64_t klo = bv | (uint64_t)(lo < 0 ? 0 : lo);
-            const uint64_t khi = bv | (hi > (int64_t)a.n ? a.n : (uint64_t)hi);
+            int64_t wlo = lo < 0 ? 0 : lo, whi = hi > (int64_t)a.n ? (int64_t)a.n : hi;
+            if (a.lay.nseq) {  // wave-uniform: both ends in one sequence, (seq_start[i], seq_start[i + 1]] of e_x
+                const uint64_t sq = layout_seq_of_end(a.lay, ex);
+                if (sq == LAYOUT_NONE) continue;
+                const int64_t s0 = (int64_t)a.lay.seq_start[sq] + 1, s1 = (int64_t)a.lay.seq_start[sq + 1];
+                wlo = wlo < s0 ? s0 : wlo;
+                whi = whi > s1 ? s1 : whi;
+                if (wlo > whi) continue;
+            }
+            const uint64_t klo = bv | (uint64_t)wlo;
+            const uint64_t khi = bv | (uint64_t)whi;
             uint64_t l = LF, h = L;
             while (l < h) {  // the first locus with klo <= lkey
                 const uint64_t mid = (l + h) >> 1;
@@ -488,6 +498,7 @@ int pair_join_batch(const sas_index* x, const MmQueries& Q, const PairCall& c, h
         j.B = B;
         j.nfwd = nq;
         j.n = x->n;
+        j.lay = x->lay;
         j.ebits = s.ebits;
         j.min_frag = min_frag;
         j.max_frag = max_frag;

@@ -26,6 +26,9 @@
 //                      chunk to one key in the layout of the join's key and a head count, and
 //                      combines them per pair with a 64-bit atomicMin and atomicAdd: integer min
 //                      and add only, so the result does not depend on the order of arrival.
+//                      On an index with a sequence layout (template bool LAY) the window is cut to
+//                      the anchor's sequence and the lane runs rs_scan_chunk_lay, which resets
+//                      at every segment's lo and skips the gap columns.
 #include "pair_path.hpp"
 
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -83,6 +86,7 @@ struct RsArgs {
     uint32_t cpa;           // chunks per anchor
     uint64_t* rmin;         // per pair: the least key (MAP_NONE before)
     uint64_t* rcnt;         // per pair: candidate runs (0 before)
+    LayoutView lay;         // LAY: the index's sequence layout
 };
 
 // The ends [c0, c1] (0 <= c0 <= c1 <= n) of the window [lo, hi] of one anchor, `first` its first
@@ -125,8 +129,76 @@ __device__ __forceinline__ void rs_scan_chunk(const RsArgs& a, const uint8_t* __
     *heads_out = heads;
 }
 
-// NW: 1, 2, 4 words of 64 rows for every read of the batch (fixed length), 0: by each partner's m
+// rs_scan_chunk on an index with a sequence layout: the columns [w0, c1) can cross several segment
+// edges.  The lane finds the first segment that ends behind w0 once and keeps its [slo, shi); it
+// resets (EdMyers::reset, score = m) before the first column of each segment, so the score is
+// D_L of sas.h; at a gap column it reports no candidate (prev = false) and jumps to the next
+// segment's lo, or to the chunk's end when no segment starts before c1, so a gap of any length
+// costs one step.  A reset does not clear prev: the end at a segment's lo belongs to the segment
+// before it when the two are adjacent.  The early exit fires only when the current segment
+// reaches the chunk's end (behind a reset the score starts again at m), and in a gap when no
+// segment starts before c1.  w0 inside a segment needs no more than before: the lead-in argument
 template <int NW>
+__device__ __forceinline__ void rs_scan_chunk_lay(const RsArgs& a, const uint8_t* __restrict__ qb, uint32_t m,
+                                                  int64_t c0, int64_t c1, int64_t first, int64_t lo, int64_t hi,
+                                                  bool rev, uint64_t base, uint64_t* best_out, uint32_t* heads_out) {
+    const int64_t kr = (int64_t)a.k_rescue, none = INT64_MAX;
+    int64_t w0 = c0 - 1 - (int64_t)m - kr;                          // the columns [w0, c1), c1 <= n
+    if (w0 < 0) w0 = 0;
+    uint64_t g = 0, gh = a.lay.nseg;
+    while (g < gh) {                                                // the segments with hi <= w0 lie before
+        const uint64_t mid = (g + gh) >> 1;
+        if ((int64_t)a.lay.seg_hi[mid] <= w0) g = mid + 1;
+        else gh = mid;
+    }
+    int64_t slo = g < a.lay.nseg ? (int64_t)a.lay.seg_lo[g] : none, shi = g < a.lay.nseg ? (int64_t)a.lay.seg_hi[g] : none;
+    uint64_t best = MAP_NONE;
+    uint32_t heads = 0;
+    EdMyers<NW> my;
+    my.init(qb, m);
+    int64_t score = m;
+    bool prev = false;
+    for (int64_t col = w0; col < c1; col += 32) {
+        uint64_t tx = text_chars32(a.tw, (uint64_t)col);            // col < c1 <= n
+        const int64_t cend = col + 32 < c1 ? col + 32 : c1;
+        for (int64_t c = col; c < cend; c++, tx <<= 2) {
+            if (c >= shi) {                                         // the next segment (they are not empty)
+                g++;
+                slo = g < a.lay.nseg ? (int64_t)a.lay.seg_lo[g] : none;
+                shi = g < a.lay.nseg ? (int64_t)a.lay.seg_hi[g] : none;
+            }
+            if (c < slo) {                                          // a gap column: its end has no D_L
+                prev = false;
+                col = (slo < c1 ? slo : c1) - 32;                   // go on at the next segment's lo, or stop:
+                break;                                              // the outer step adds the 32 and reloads tx
+            }
+            if (c == slo) {
+                my.reset();
+                score = m;
+            }
+            score += my.column(tx);
+            const int64_t e = c + 1;
+            const bool cand = score <= kr;
+            if (cand && e >= c0) {
+                const uint64_t key = base + ((uint64_t)score << PR_SUM_SHIFT) +
+                                     (rev ? ((uint64_t)e << PR_EX_SHIFT) + (uint64_t)(hi - e) : (uint64_t)(e - lo));
+                best = key < best ? key : best;
+                heads += !prev || e == first ? 1u : 0u;
+            }
+            prev = cand;
+            if (shi >= c1 && score - (c1 - e) > kr) {               // out of reach for every later end
+                col = c1;
+                break;
+            }
+        }
+    }
+    *best_out = best;
+    *heads_out = heads;
+}
+
+// NW: 1, 2, 4 words of 64 rows for every read of the batch (fixed length), 0: by each partner's m.
+// LAY: the index has a sequence layout; without one the instructions are those from before
+template <int NW, bool LAY>
 __global__ __launch_bounds__(RS_BLOCK) void k_pair_rescue(RsArgs a) {
     const uint64_t items = *a.na * (uint64_t)a.cpa;
     const uint64_t emask = (1ull << a.ebits) - 1ull;
@@ -145,11 +217,19 @@ __global__ __launch_bounds__(RS_BLOCK) void k_pair_rescue(RsArgs a) {
         // the window of the partner's ends, and this item's chunk of it
         const int64_t lo = rev ? ea + (int64_t)mb - (int64_t)a.max_frag : ea - (int64_t)ma + (int64_t)a.min_frag;
         const int64_t hi = lo + spread;
-        const int64_t first = lo > 0 ? lo : 0;
+        int64_t first = lo > 0 ? lo : 0;
         int64_t c0 = lo + ch * (int64_t)RS_CHUNK, c1 = c0 + (int64_t)RS_CHUNK - 1;
         if (c1 > hi) c1 = hi;
         if (c1 > n) c1 = n;
         if (c0 < 0) c0 = 0;
+        if (LAY) {  // the window is cut to the anchor's sequence, (seq_start[i], seq_start[i + 1]]
+            const uint64_t sq = layout_seq_of_end(a.lay, (uint64_t)ea);
+            if (sq == LAYOUT_NONE) continue;
+            const int64_t s0 = (int64_t)a.lay.seq_start[sq] + 1, s1 = (int64_t)a.lay.seq_start[sq + 1];
+            if (first < s0) first = s0;
+            if (c0 < s0) c0 = s0;
+            if (c1 > s1) c1 = s1;
+        }
         if (c0 > c1) continue;
         const uint64_t o = (rev ? rb : r) & 1ull;                   // f - 2 i of the forward mate
         const uint64_t base = ((uint64_t)a.ldist[l] << PR_SUM_SHIFT) | (o << PR_O_SHIFT) |
@@ -157,7 +237,13 @@ __global__ __launch_bounds__(RS_BLOCK) void k_pair_rescue(RsArgs a) {
         const uint8_t* qb = a.B.qbytes + a.B.off(bb);
         uint64_t best = MAP_NONE;
         uint32_t heads = 0;
-        if (NW == 1 || (NW == 0 && mb <= 64)) rs_scan_chunk<1>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
+        if (LAY) {
+            if (NW == 1 || (NW == 0 && mb <= 64))
+                rs_scan_chunk_lay<1>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
+            else if (NW == 2 || (NW == 0 && mb <= 128))
+                rs_scan_chunk_lay<2>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
+            else rs_scan_chunk_lay<4>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
+        } else if (NW == 1 || (NW == 0 && mb <= 64)) rs_scan_chunk<1>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
         else if (NW == 2 || (NW == 0 && mb <= 128))
             rs_scan_chunk<2>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
         else rs_scan_chunk<4>(a, qb, mb, c0, c1, first, lo, hi, rev, base, &best, &heads);
@@ -226,10 +312,16 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
         // the grid is capped and strides over the item count, which stays on the device
         const uint64_t upper = P * (uint64_t)a.cpa;
         const dim3 rgrid(tile_grid(std::min(grid_for(upper, RS_BLOCK), (unsigned)x->num_cus * 8)));
-        if (B.qoff) hipLaunchKernelGGL(k_pair_rescue<0>, rgrid, dim3(RS_BLOCK), 0, st, a);
-        else if (B.m <= 64) hipLaunchKernelGGL(k_pair_rescue<1>, rgrid, dim3(RS_BLOCK), 0, st, a);
-        else if (B.m <= 128) hipLaunchKernelGGL(k_pair_rescue<2>, rgrid, dim3(RS_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_pair_rescue<4>, rgrid, dim3(RS_BLOCK), 0, st, a);
+        a.lay = x->lay;
+        if (x->lay.nseq) {
+            if (B.qoff) hipLaunchKernelGGL((k_pair_rescue<0, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
+            else if (B.m <= 64) hipLaunchKernelGGL((k_pair_rescue<1, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
+            else if (B.m <= 128) hipLaunchKernelGGL((k_pair_rescue<2, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((k_pair_rescue<4, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        } else if (B.qoff) hipLaunchKernelGGL((k_pair_rescue<0, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        else if (B.m <= 64) hipLaunchKernelGGL((k_pair_rescue<1, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        else if (B.m <= 128) hipLaunchKernelGGL((k_pair_rescue<2, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_pair_rescue<4, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
         HIP_TRY(hipGetLastError());
     }
     return pair_finish<true>(x, c, ps, rmin, rcnt, o, st, flags);

@@ -48,6 +48,7 @@ SAS_PAIR_RESCUED = 2  # sas_map_pairs_rescue's per-pair flags
 SAS_PAIR_RESCUE_SKIPPED = 4
 SAS_MAP_RESCUED = 8  # its per-read flag, beside the SAS_ED_* bits of out_qflags
 SAS_RESCUE_CHUNK = 128  # window ends per work item of its scan
+SAS_SEQ_NONE = 0xFFFFFFFF  # sas_translate: the interval lies in no one segment
 SAS_BUILD_WIDE = 1 << 6
 SAS_BUILD_SECTOR = 1 << 7
 SAS_BUILD_SA40 = 1 << 8
@@ -212,6 +213,12 @@ def lib():
     L.sas_map_pairs_rescue_fixed.argtypes = [vp, vp, u32, u64, u32, u32, u64, u32, u32, u64] + [vp] * 14 + [u32]
     L.sas_copy_sa64.argtypes = [vp, u64, u64, vp, u32]
     L.sas_read_fasta.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64)]
+    L.sas_check_layout.argtypes = [u64, vp, u64, vp, vp, u64]
+    L.sas_set_layout.argtypes = [vp, vp, u64, vp, vp, u64]
+    L.sas_get_layout.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]
+    L.sas_translate.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32]
+    L.sas_read_fasta_layout.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp, vp, u64,
+                                        C.POINTER(u64), vp, u64, C.POINTER(u64)]
     L.sas_kmer_keys.argtypes = [vp, u64, u32, u64, vp, C.POINTER(u64), u32]
     L.sas_verify.argtypes = [vp]
     L.sas_search_batch.argtypes = [vp, vp, vp, vp, u64, i32, vp, vp, vp, u32]

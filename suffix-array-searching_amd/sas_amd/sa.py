@@ -259,6 +259,65 @@ class SaNaive:
         check(lib().sas_copy_sa64(self._h, self.rank_lo + start, count, out.ctypes.data, 0))
         return out[:count]
 
+    # -- the sequence layout (sas.h: sas_set_layout): each segment is a text of its own for the
+    #    approximate calls; exact lookups ignore it
+    def set_layout(self, seq_start=None, seg_lo=(), seg_hi=()):
+        """Set the index's sequence layout from host arrays (sas_set_layout: seq_start has one more
+        entry than sequences, from 0 to n; the segments [seg_lo[i], seg_hi[i]) are the real bases),
+        or clear it with seq_start=None.  No call may be in flight on the index."""
+        if seq_start is None:
+            check(lib().sas_set_layout(self._h, None, 0, None, None, 0))
+            return
+        s = np.ascontiguousarray(seq_start, np.uint64)
+        lo, hi = np.ascontiguousarray(seg_lo, np.uint64), np.ascontiguousarray(seg_hi, np.uint64)
+        if len(s) < 2 or len(lo) != len(hi):
+            raise ValueError("set_layout: seq_start needs at least two entries, seg_lo and seg_hi equal lengths")
+        check(lib().sas_set_layout(self._h, s.ctypes.data, len(s) - 1, lo.ctypes.data if len(lo) else None,
+                                   hi.ctypes.data if len(hi) else None, len(lo)))
+
+    def layout(self):
+        """(seq_start, seg_lo, seg_hi) as numpy uint64 arrays (sas_get_layout), or None without one."""
+        nseq, nseg = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sas_get_layout(self._h, C.byref(nseq), C.byref(nseg), None, None, None))
+        if nseq.value == 0:
+            return None
+        s = np.zeros(nseq.value + 1, np.uint64)
+        lo, hi = np.zeros(max(nseg.value, 1), np.uint64), np.zeros(max(nseg.value, 1), np.uint64)
+        check(lib().sas_get_layout(self._h, None, None, s.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+        return s, lo[: nseg.value], hi[: nseg.value]
+
+    def translate(self, pos, span=None, u32: bool = False, stream=None):
+        """Text positions to (sequence id, offset in it) (sas_translate): the id is SAS_SEQ_NONE, and
+        the offset the position itself, unless [pos, pos + span) (span None: 1) lies inside one
+        segment.  torch CUDA tensors (pos int64, or int32 with u32; span int32) -> CUDA tensors
+        (int32 ids holding the u32 bits, offsets in pos's dtype), asynchronous; numpy -> numpy."""
+        L = lib()
+        if _is_cuda(pos):
+            import torch
+            dt = torch.int32 if u32 else torch.int64
+            if pos.dtype != dt or (span is not None and (not _is_cuda(span) or span.dtype != torch.int32)):
+                raise ValueError(f"translate: pos must be a CUDA {dt} tensor and span a CUDA int32 tensor")
+            pos = pos.contiguous()
+            span = None if span is None else span.contiguous()
+            cnt = int(pos.numel())
+            if span is not None and int(span.numel()) != cnt:
+                raise ValueError("translate: one span per position")
+            seq = torch.empty(cnt, dtype=torch.int32, device=pos.device)
+            off = torch.empty(cnt, dtype=dt, device=pos.device)
+            st = stream if stream is not None else torch.cuda.current_stream(pos.device).cuda_stream
+            check(L.sas_translate(self._h, _ptr(pos), _ptr(span), cnt, _ptr(seq), _ptr(off), st,
+                                  _lib.SAS_DEVICE_PTRS | (_lib.SAS_LOCATE_U32 if u32 else 0)))
+            return seq, off
+        pos = np.ascontiguousarray(pos, np.uint32 if u32 else np.uint64)
+        span = None if span is None else np.ascontiguousarray(span, np.uint32)
+        if span is not None and len(span) != len(pos):
+            raise ValueError("translate: one span per position")
+        seq = np.zeros(len(pos), np.uint32)
+        off = np.zeros(len(pos), pos.dtype)
+        check(L.sas_translate(self._h, _ptr(pos), _ptr(span), len(pos), _ptr(seq), _ptr(off), stream,
+                              _lib.SAS_LOCATE_U32 if u32 else 0))
+        return seq, off
+
     def lcp_array(self) -> np.ndarray:
         out = np.zeros(self.sa_n, np.uint32)
         check(lib().sas_copy_lcp(self._h, out.ctypes.data, self.sa_n, 0))
@@ -1170,6 +1229,44 @@ def read_fasta_file(path: str) -> np.ndarray:
     out = np.zeros(max(n.value, 1), np.uint8)
     check(lib().sas_read_fasta(path.encode(), out.ctypes.data, n.value, C.byref(n)))
     return out[: n.value]
+
+
+# sas_amd.read_fasta_layout: the text, and what SaNaive.set_layout takes
+FastaLayout = namedtuple("FastaLayout", "text seq_start seg_lo seg_hi names")
+
+
+def read_fasta_layout(path: str) -> FastaLayout:
+    """sas_read_fasta_layout: read_fasta_file's bytes, the start of every record (seq_start, one
+    more entry than records), the maximal runs of ACGTacgt as segments [seg_lo, seg_hi) and the
+    first word of every header."""
+    L = lib()
+    n, nseq, nseg, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    p = path.encode()
+    check(L.sas_read_fasta_layout(p, None, 0, C.byref(n), None, 0, C.byref(nseq), None, None, 0, C.byref(nseg),
+                                  None, 0, C.byref(nl)))
+    out = np.zeros(max(n.value, 1), np.uint8)
+    starts = np.zeros(nseq.value + 1, np.uint64)
+    lo, hi = np.zeros(max(nseg.value, 1), np.uint64), np.zeros(max(nseg.value, 1), np.uint64)
+    names = C.create_string_buffer(max(nl.value, 1))
+    check(L.sas_read_fasta_layout(p, out.ctypes.data, n.value, C.byref(n), starts.ctypes.data, len(starts),
+                                  C.byref(nseq), lo.ctypes.data, hi.ctypes.data, nseg.value, C.byref(nseg),
+                                  C.cast(names, C.c_void_p), nl.value, C.byref(nl)))
+    words = names.raw[: nl.value].split(b"\0")[:-1] if nl.value else []
+    return FastaLayout(out[: n.value], starts, lo[: nseg.value], hi[: nseg.value], [w.decode() for w in words])
+
+
+def _u64(x):
+    return np.ascontiguousarray(x, np.uint64)
+
+
+def check_layout(n: int, seq_start, seg_lo, seg_hi) -> None:
+    """sas_check_layout (no device call): raises SasError (EINVAL) naming the entry that breaks a
+    rule of sas.h's sequence layout."""
+    s, lo, hi = _u64(seq_start), _u64(seg_lo), _u64(seg_hi)
+    if len(lo) != len(hi):
+        raise ValueError("seg_lo and seg_hi differ in length")
+    check(lib().sas_check_layout(int(n), s.ctypes.data if len(s) else None, max(len(s), 1) - 1,
+                                 lo.ctypes.data if len(lo) else None, hi.ctypes.data if len(hi) else None, len(lo)))
 
 
 def kmer_keys(t, k: int = 16, limit: int | None = None) -> np.ndarray:
