@@ -144,7 +144,7 @@ struct sas_index {
     uint32_t prefix_chars = 0;    // prefix_key_lo + j; prefix_w bytes per entry (4: u32; 5: packed
     uint32_t prefix_w = 4;        // 40-bit, for a 40-bit SA; 16 G: G inline slots)
     uint64_t prefix_key_lo = 0;   // whole index: 0 and 4^p + 1 entries; a part (a rank range of the
-    uint64_t prefix_entries = 0;  // SA): its first key .. its last key + 2 (pt_slot, sas_search.hip)
+    uint64_t prefix_entries = 0;  // SA): its first key .. its last key + 2 (pt_slot below)
     bool prefix_hi40 = false;     // inline slots of a text >= 2^32 chars: bits 32..39 of each slot's SA
                                   // value in slot 1's rank word (only slot 0's rank is read); with two
                                   // slots also bits 32..39 of slot 0's rank (a part of >= 2^32 suffixes)
@@ -212,7 +212,7 @@ struct sas_index {
 };
 
 // The index's stream-ordered scratch pool (created on first use, destroyed by sas_free):
-// sas_route_pack and the sas_locate calls allocate from it (sas_search.hip)
+// sas_route_pack and the sas_locate calls allocate from it (sas_route.hip)
 int sas_scratch_pool(const sas_index* x, hipMemPool_t* out);
 
 struct sst_index {
@@ -389,7 +389,7 @@ __device__ __forceinline__ uint32_t quad_mask(bool b) {
 // ---------------------------------------------------------------- device helpers
 // Non-temporal loads for arrays far larger than the 256 MiB Infinity Cache (more than
 // SAS_NT_BYTES): they then do not evict the upper tree layers from L2.  Measured on the
-// quad tree (sas_search.hip, quad_nt_from): -6% at n = 2^30; on a level that partly
+// quad tree (search_quad.hip, quad_nt_from): -6% at n = 2^30; on a level that partly
 // fits the Infinity Cache (554 MB) they made the kernel slower.
 #ifndef SAS_NT_BYTES
 #define SAS_NT_BYTES (3ull * (256ull << 20))

@@ -1,4 +1,4 @@
-// The ALU-only bisect step of k_sa_quad_llcp's walk (sas_search.hip), on the host and on the
+// The ALU-only bisect step of k_sa_quad_llcp's walk (search_quad_llcp.hip), on the host and on the
 // device, so that tests/cpp/qllcp_bisect_check.cpp can drive the very code the kernel runs.
 //
 // The walk bisects [l, r) of the SA's ranks like binary_search (sas/sa_search.rs:98-112), but

@@ -1024,7 +1024,7 @@ static int build_prefix(sas_index* x, uint32_t p, uint32_t inl) {
     // plus two entries of rank sa_n.  Keys are monotone over the ranks (zero padding), so a
     // part's suffixes are exactly that interval's, and a query outside it clamps to a
     // neighbouring entry whose suffixes are all > q (below) or to rank sa_n (above)
-    // (pt_slot, sas_search.hip).  At 8 parts of a random text: 1/8 of the 4^p keys each
+    // (pt_slot, common.hpp).  At 8 parts of a random text: 1/8 of the 4^p keys each
     uint64_t base = 0, entries = (1ull << (2 * p)) + 1;
     if (sa_n < x->n) {
         const uint32_t sh = 64 - 2 * p;

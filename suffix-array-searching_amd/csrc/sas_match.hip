@@ -30,7 +30,7 @@
 #include <type_traits>
 #include <vector>
 
-// k_sa_binary's workgroup (sas_search.hip SAS_BIN_BLOCK / SAS_BIN_BPC): 768 lanes, two
+// k_sa_binary's workgroup (search_args.hpp SAS_BIN_BLOCK / SAS_BIN_BPC): 768 lanes, two
 // workgroups a CU, 6 waves per SIMD -> at most 80 VGPRs
 #define MATCH_BLOCK 768
 #define MATCH_BPC 2

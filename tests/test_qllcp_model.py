@@ -1,4 +1,4 @@
-"""The soundness argument of SAS_ALGO_QUAD_LLCP (k_sa_quad_llcp, csrc/sas_search.hip) on the CPU:
+"""The soundness argument of SAS_ALGO_QUAD_LLCP (k_sa_quad_llcp, csrc/search_quad_llcp.hip) on the CPU:
 tools/qllcp_model.py restates the kernel's routing invariants (leaf k of the first suffix whose
 16-char key is >= K16, the leaf of K16 + 1), its leaf counts, L0 / U / s0 / kappa and the LLCP
 walk with its substituted lcps; every tie compare asserts that the chars it skips equal q's,

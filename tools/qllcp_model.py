@@ -1,4 +1,4 @@
-"""CPU model of k_sa_quad_llcp (SAS_ALGO_QUAD_LLCP, csrc/sas_search.hip) for m > 32: the
+"""CPU model of k_sa_quad_llcp (SAS_ALGO_QUAD_LLCP, csrc/search_quad_llcp.hip) for m > 32: the
 quad tree's routing invariants (leaf k = the leaf of the first suffix whose 16-char key is
 >= K16; leaf kU = that of the first key16 > K16), the leaf counts, L0 / U / s0 / kappa, and the
 LLCP walk with its substituted lcps.  Every tie compare asserts that the chars it skips are
