@@ -1,5 +1,6 @@
-// build_util.hpp -- host helpers shared by the index builders (sas_build.hip,
-// sas_build40.hip): launch sizing, owning device buffers, error plumbing.
+// build_util.hpp -- host helpers shared by the index builders (sas_build.hip, the build_*.hip
+// units, sas_build40.hip) and the calls: launch sizing, owning device buffers, rocPRIM's
+// temp buffer, error plumbing.  The builders' own steps are declared in build_steps.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -71,12 +72,27 @@ struct DevBuf {
 
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+// rocPRIM's two calls: fn(nullptr, size) asks for the temp size, fn(tmp.p, size) does the work.
+// `have` is tmp's size so far and only grows, so the calls of a loop share one allocation
+template <class Fn>
+static int with_temp(DevBuf& tmp, size_t& have, const char* what, Fn fn) {
+    size_t need = 0;
+    HIP_TRY(fn((void*)nullptr, need));
+    if (need > have || !tmp.p) {
+        TRY(tmp.alloc(need, what));
+        have = need;
+    }
+    HIP_TRY(fn(tmp.p, need));
+    return 0;
+}
+// a temp buffer of this call's own size, in place of tmp's last one (the u32 SA builder)
+template <class Fn>
+static int with_temp(DevBuf& tmp, const char* what, Fn fn) {
+    size_t none = 0;
+    return with_temp(tmp, none, what, fn);
+}
 
-// Declared here, defined in sas_build40.hip: the bucketed builder of a packed
-// 40-bit SA (n up to 2^40 as HBM allows).  sa5: device, 5*n + SAS_SA40_PAD bytes.
-int build_sa_gpu40(const uint64_t* tw, uint64_t n, uint8_t* sa5, uint32_t* rounds_out, uint64_t* buckets_out);
-// Part builder (sas_build_part): the SA rank range of part `part` of `parts`
-// (contiguous 7-mer bins), packed 40-bit; returns the device buffer, the range and
-// SA[rank_hi] (n if none).
-int build_sa_part40(const uint64_t* tw, uint64_t n, uint32_t part, uint32_t parts, uint8_t** sa5_out,
-                    uint64_t* rank_lo, uint64_t* count, uint64_t* next_pos, uint32_t* rounds_out);
+// table fills (prefix table, bucket table): a rank fills a key gap of up to PT_SMALL entries
+// itself; a longer one goes to a list that whole workgroups fill
+#define PT_SMALL 256
+

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <errno.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "layout.hpp"
@@ -148,7 +149,7 @@ struct sas_index {
     bool prefix_hi40 = false;     // inline slots of a text >= 2^32 chars: bits 32..39 of each slot's SA
                                   // value in slot 1's rank word (only slot 0's rank is read); with two
                                   // slots also bits 32..39 of slot 0's rank (a part of >= 2^32 suffixes)
-    uint4* llcp = nullptr;        // SAS_BUILD_LLCP: {SA[m], Llcp, Rlcp, 2 x 16 chars} per rank m (sas_build.hip)
+    uint4* llcp = nullptr;        // SAS_BUILD_LLCP: {SA[m], Llcp, Rlcp, 2 x 16 chars} per rank m (build_lcp.hip)
     uint32_t* stree = nullptr;   // all nodes, 16 u32 each
     uint64_t stree_nodes = 0;
     uint32_t stree_height = 0;
@@ -246,7 +247,7 @@ struct sst_index {
 #define SAS_LLCP_CAP 4095u
 
 // W = 8: the tagged SA of SAS_BUILD_TAGGED, u64 entries {SA 40 bits | 12 chars << 40}
-// (sas_build.hip, build_tagged): the SA value is the low 40 bits.
+// (build_tagged.hip, build_tagged): the SA value is the low 40 bits.
 #define SAS_TAG_CHARS 12
 // Bucket lines (SAS_BUILD_TAG_LINES): 20 entries of 48 bits per 128-B line, {SA | tag << sb}
 // with sb = max(32, bit length of n) SA bits and 48 - sb tag bits (the bits of chars [p, ...)
@@ -299,6 +300,14 @@ struct SaView {
     }
 };
 
+// The plain SA's entry width (sas_index::sa_w: 5 = packed 40-bit, else u32) as a compile-time
+// constant, f(std::integral_constant<int, W>): one launch serves both widths
+template <class F>
+void with_sa_w(uint32_t sa_w, F&& f) {
+    if (sa_w == 5) f(std::integral_constant<int, 5>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
 // Writes: byte stores, so neighbouring entries written by other lanes never race.
 template <int W>
 __device__ __forceinline__ void sa_put(uint8_t* p, uint64_t i, uint64_t v) {
@@ -318,7 +327,7 @@ __device__ __forceinline__ void sa_put(uint8_t* p, uint64_t i, uint64_t v) {
 // ---------------------------------------------------------------- prefix table lookups
 // The SAS_BUILD_PREFIX table as a lookup reads it (the kernels' argument structs fill one):
 // entry j = the first rank whose p-char key (zero padded past a suffix's end, so key order is
-// SA order) is >= base + j, in any of the entry formats of build_prefix (sas_build.hip)
+// SA order) is >= base + j, in any of the entry formats of build_prefix (build_prefix.hip)
 struct PrefixView {
     const uint8_t* prefix;   // u32 or packed 40-bit entries, or 16 G-byte inline ones
     uint32_t prefix_chars;

@@ -24,6 +24,7 @@
 // + ~60 B per tied suffix.  A single HIST_BITS bin larger than cap (a text
 // dominated by one 7-mer) is refused with ENOTSUP rather than overcommitting.
 #include "build_util.hpp"
+#include "build_steps.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -208,18 +209,6 @@ __global__ void k_r40_assign(uint64_t cnt, const uint64_t* __restrict__ vals, co
     }
 }
 
-template <class Fn>
-static int with_temp(DevBuf& tmp, size_t& have, Fn fn) {
-    size_t need = 0;
-    HIP_TRY(fn((void*)nullptr, need));
-    if (need > have) {
-        TRY(tmp.alloc(need, "rocprim temp"));
-        have = need;
-    }
-    HIP_TRY(fn(tmp.p, need));
-    return 0;
-}
-
 static int histogram(const uint64_t* tw, uint64_t n, std::vector<uint64_t>& h) {
     DevBuf hist;
     TRY(hist.alloc(HIST_BINS * 8, "histogram"));
@@ -295,7 +284,7 @@ static int sort_bins_into(const uint64_t* tw, uint64_t n, const std::vector<uint
         const dim3 cg(collect_grid(nblk));
         hipLaunchKernelGGL(k_bucket_count, cg, dim3(COLLECT_BLOCK), 0, st, tw, n, blo, bhi,
                            bcnt.as<uint64_t>());
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::exclusive_scan(t, sz, bcnt.as<uint64_t>(), bcnt.as<uint64_t>(), (uint64_t)0,
                                            (size_t)nblk, rocprim::plus<uint64_t>(), st);
         }));
@@ -303,7 +292,7 @@ static int sort_bins_into(const uint64_t* tw, uint64_t n, const std::vector<uint
                            bcnt.as<uint64_t>(), ka.as<uint64_t>(), va.as<uint64_t>());
         rocprim::double_buffer<uint64_t> kdb(ka.as<uint64_t>(), kb.as<uint64_t>());
         rocprim::double_buffer<uint64_t> vdb(va.as<uint64_t>(), vb.as<uint64_t>());
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::radix_sort_pairs(t, sz, kdb, vdb, (size_t)c, 0, 64, st);
         }));
         const uint64_t* sk = kdb.current();
@@ -311,20 +300,20 @@ static int sort_bins_into(const uint64_t* tw, uint64_t n, const std::vector<uint
         uint64_t* free_k = (sk == ka.as<uint64_t>()) ? kb.as<uint64_t>() : ka.as<uint64_t>();
         uint64_t* free_v = (sv == va.as<uint64_t>()) ? vb.as<uint64_t>() : va.as<uint64_t>();
         hipLaunchKernelGGL(k_b_heads, dim3(grid_for(c)), dim3(256), 0, st, sk, c, off, grp.as<uint64_t>());
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::inclusive_scan(t, sz, grp.as<uint64_t>(), grp.as<uint64_t>(), (size_t)c, MaxOp64(), st);
         }));
         hipLaunchKernelGGL(k_b_emit, dim3(grid_for(c)), dim3(256), 0, st, sk, sv, grp.as<uint64_t>(), c, off, sa5,
                            rank5, flg.as<uint8_t>());
         HIP_TRY(hipGetLastError());
         rocprim::counting_iterator<uint64_t> cit(off);
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::select(t, sz, cit, flg.as<uint8_t>(), free_k, cnt_d.as<uint64_t>(), (size_t)c, st);
         }));
         uint64_t d = 0;
         HIP_TRY(hipMemcpy(&d, cnt_d.p, 8, hipMemcpyDeviceToHost));
         if (d) {
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::select(t, sz, grp.as<uint64_t>(), flg.as<uint8_t>(), free_v, cnt_d.as<uint64_t>(),
                                        (size_t)c, st);
             }));
@@ -396,26 +385,26 @@ int build_sa_gpu40(const uint64_t* tw, uint64_t n, uint8_t* sa5, uint32_t* round
                                rk.as<uint64_t>(), rv.as<uint64_t>());
             rocprim::double_buffer<uint64_t> k2(rk.as<uint64_t>(), rk2.as<uint64_t>());
             rocprim::double_buffer<uint64_t> v2(rv.as<uint64_t>(), rv2.as<uint64_t>());
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::radix_sort_pairs(t, sz, k2, v2, (size_t)cnt, 0, 41, st);
             }));
             hipLaunchKernelGGL(k_r40_group, dim3(grid_for(cnt)), dim3(256), 0, st, v2.current(), cnt, rkv,
                                k2.current());
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::radix_sort_pairs(t, sz, k2, v2, (size_t)cnt, 0, 40, st);
             }));
             const uint64_t* sv = v2.current();
             hipLaunchKernelGGL(k_r40_heads, dim3(grid_for(cnt)), dim3(256), 0, st, sv, cnt, rkv, n, hh, L,
                                hp.as<uint64_t>(), hd.as<uint8_t>());
             hipLaunchKernelGGL(k_r40_scatter, dim3(grid_for(cnt)), dim3(256), 0, st, L, cnt, sv, sa5);
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::inclusive_scan(t, sz, hp.as<uint64_t>(), hp.as<uint64_t>(), (size_t)cnt, MaxOp64(),
                                                st);
             }));
             hipLaunchKernelGGL(k_r40_assign, dim3(grid_for(cnt)), dim3(256), 0, st, cnt, sv, hp.as<uint64_t>(),
                                hd.as<uint8_t>(), rank.as<uint8_t>(), uf.as<uint8_t>());
             HIP_TRY(hipGetLastError());
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::select(t, sz, L, uf.as<uint8_t>(), Ln, cnt_d.as<uint64_t>(), (size_t)cnt, st);
             }));
             HIP_TRY(hipMemcpy(&cnt, cnt_d.p, 8, hipMemcpyDeviceToHost));
@@ -537,7 +526,7 @@ static int resolve_ties_windows(const uint64_t* tw, uint64_t n, uint8_t* sa5, De
             rocprim::double_buffer<uint64_t> kd(kbuf.as<uint64_t>(), kbuf2.as<uint64_t>());
             rocprim::double_buffer<uint64_t> vd(pa, pb);
             const int nb = bits[pass];
-            TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+            TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
                 return rocprim::radix_sort_pairs(t, sz, kd, vd, (size_t)cnt, 0, nb, st);
             }));
             if (vd.current() != pa) { uint64_t* t = pa; pa = pb; pb = t; }
@@ -546,14 +535,14 @@ static int resolve_ties_windows(const uint64_t* tw, uint64_t n, uint8_t* sa5, De
                            lc.as<uint64_t>(), L, hp.as<uint64_t>(), hd.as<uint8_t>());
         hipLaunchKernelGGL(k_w_scatter, dim3(grid_for(cnt)), dim3(256), 0, st, L, pa, pos.as<uint64_t>(), cnt,
                            hd.as<uint8_t>(), sa5, uf.as<uint8_t>());
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::inclusive_scan(t, sz, hp.as<uint64_t>(), hp.as<uint64_t>(), (size_t)cnt, MaxOp64(), st);
         }));
         HIP_TRY(hipGetLastError());
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::select(t, sz, hp.as<uint64_t>(), uf.as<uint8_t>(), Gn, cnt_d.as<uint64_t>(), (size_t)cnt, st);
         }));
-        TRY(with_temp(tmp, tmp_have, [&](void* t, size_t& sz) {
+        TRY(with_temp(tmp, tmp_have, "rocprim temp", [&](void* t, size_t& sz) {
             return rocprim::select(t, sz, L, uf.as<uint8_t>(), Ln, cnt_d.as<uint64_t>(), (size_t)cnt, st);
         }));
         HIP_TRY(hipMemcpy(&cnt, cnt_d.p, 8, hipMemcpyDeviceToHost));

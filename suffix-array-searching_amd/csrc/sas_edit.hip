@@ -259,13 +259,11 @@ extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
 // a kernel of its own for an index with a layout: without one the parent's instructions run
 template <int NW>
 static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, const EdArgs& a) {
-    if (x->lay.nseq) {
-        if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_ed_verify<4, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
-    } else {
-        if (x->sa_w == 5) hipLaunchKernelGGL((k_ed_verify<5, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_ed_verify<4, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
-    }
+    with_sa_w(x->sa_w, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if (x->lay.nseq) hipLaunchKernelGGL((k_ed_verify<W, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_ed_verify<W, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
+    });
 }
 
 // All arrays on the device (out_total may be null).  Two host reads: the candidate total and

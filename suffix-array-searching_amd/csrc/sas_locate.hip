@@ -303,10 +303,10 @@ extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uin
                     lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
     else if (x->sa_w == 8)
         launch_fill(u32, grid, st, SaView<8>{x->sa}, x, lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
-    else if (x->sa_w == 5)
-        launch_fill(u32, grid, st, SaView<5>{x->sa}, x, lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
     else
-        launch_fill(u32, grid, st, SaView<4>{x->sa}, x, lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
+        with_sa_w(x->sa_w, [&](auto W) {
+            launch_fill(u32, grid, st, SaView<decltype(W)::value>{x->sa}, x, lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
+        });
     hipError_t e = hipGetLastError();
     if (tile_q) HIP_TRY(hipFreeAsync(tile_q, st));
     HIP_TRY(e);

@@ -15,7 +15,7 @@
 //     p chars (one read, any entry format: common.hpp prefix_range) instead of [0, n);
 //   * every compare starts at min(llcp, rlcp) of the bounds it has PROBED.  The table's range
 //     ends were never probed and count as lcp 0: a suffix shorter than p chars is keyed zero
-//     padded (build_prefix, sas_build.hip), so a bucket may hold a suffix that shares fewer
+//     padded (build_prefix, build_prefix.hip), so a bucket may hold a suffix that shares fewer
 //     than p chars with q (text ..AC$, p = 4, q = ACAAG: suffix AC sits in bucket ACAA);
 //   * a bound the search never moved (the table's range end; both, for an empty bucket) has no
 //     tracked lcp: one direct compare of that neighbour suffix measures it.  The compare is
@@ -242,8 +242,7 @@ static int match_device(const char* fn, const sas_index* x, int mode, const uint
     const uint64_t capb = (uint64_t)x->num_cus * MATCH_BPC;
     if (blocks > capb) blocks = capb;
     const int qw = match_qw(maxlen);
-    if (x->sa_w == 5) launch_match_w<5>(qw, dim3((unsigned)blocks), st, a);
-    else launch_match_w<4>(qw, dim3((unsigned)blocks), st, a);
+    with_sa_w(x->sa_w, [&](auto W) { launch_match_w<decltype(W)::value>(qw, dim3((unsigned)blocks), st, a); });
     HIP_TRY(hipGetLastError());
     if (ranges) {
         const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_RANGE_NO_INLINE)) | SAS_DEVICE_PTRS;

@@ -156,13 +156,11 @@ __global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
 
 template <bool LAY>
 static void mm_launch_verify(const sas_index* x, bool pre, dim3 grid, hipStream_t st, const MmArgs& a) {
-    if (x->sa_w == 5) {
-        if (pre) hipLaunchKernelGGL((k_mm_verify<5, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mm_verify<5, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-    } else {
-        if (pre) hipLaunchKernelGGL((k_mm_verify<4, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mm_verify<4, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-    }
+    with_sa_w(x->sa_w, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if (pre) hipLaunchKernelGGL((k_mm_verify<W, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_mm_verify<W, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
+    });
 }
 
 struct MmAccept {

@@ -287,7 +287,7 @@ __global__ __launch_bounds__(SEARCH_BLOCK, 8) void k_sa_tagged_range(SearchArgs 
 }
 
 // ------------------------------------------------------------------ TAGGED on bucket lines
-// SAS_BUILD_TAG_LINES (sas_build.hip, build_tag_lines): line b holds bucket b's header
+// SAS_BUILD_TAG_LINES (build_tagged.hip, build_tag_lines): line b holds bucket b's header
 // {overflow offset | count} and the 48-bit entries {SA | tag << sb} of ranks first .. first +
 // 19 (common.hpp: u16 high halves, then u32 low halves), so the bucket word and the first
 // window of the tagged lookup above are one 128-B request, and 20 slots keep 98% of the

@@ -1,6 +1,6 @@
 """A catalogue of wrong suffix arrays for the SA verifier, checked here on the CPU.
 
-sas_verify / SAS_BUILD_VERIFY (k_verify_adj in csrc/sas_build.hip) compare the suffixes of adjacent
+sas_verify / SAS_BUILD_VERIFY (k_verify_adj in csrc/build_lcp.hip) compare the suffixes of adjacent
 ranks 32 chars at a time, mask the last block, and let the lengths decide when the compare runs off
 the shorter suffix.  A wrong array tests one of those edges only if no other pair gives it away, so
 the catalogue is built from adjacent swaps: in a true SA the suffixes strictly increase, and swapping
