@@ -209,11 +209,11 @@ struct sas_index {
     uint64_t* lay_dev = nullptr;
     std::vector<uint64_t> lay_host;
     mutable StagePool* stage = nullptr;  // created by the first host-pointer search
-    mutable hipMemPool_t route_pool = nullptr;  // stream-ordered scratch of sas_route_pack (first use)
+    mutable hipMemPool_t scratch_pool = nullptr;  // stream-ordered scratch of the calls (first use)
 };
 
 // The index's stream-ordered scratch pool (created on first use, destroyed by sas_free):
-// sas_route_pack and the sas_locate calls allocate from it (sas_route.hip)
+// sas_route_pack, the sas_locate calls and what builds on them allocate from it (sas_index.hip)
 int sas_scratch_pool(const sas_index* x, hipMemPool_t* out);
 
 struct sst_index {

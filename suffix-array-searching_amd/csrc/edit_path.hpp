@@ -7,7 +7,7 @@
 // stays in the state
 struct EdState {
     SeedState seed;
-    MmPoolBuf mask, kbase, dists, pscan, keys, vals, uscan;
+    PoolBuf mask, kbase, dists, pscan, keys, vals, uscan;
     const uint64_t* skeys = nullptr;  // the P sorted proposals, key = (query << ebits) | end;
     const uint8_t* svals = nullptr;   // their distances (equal keys carry equal distances)
     uint64_t C = 0, P = 0;            // P == 0: nothing was proposed, skeys / svals are null

@@ -67,7 +67,7 @@ __device__ __forceinline__ uint32_t map_clamp32(uint64_t v) {
 struct MapState {
     MmQueries B;                // the batch: nb = copies nq queries
     uint64_t nb = 0;
-    MmPoolBuf bbytes, bscan, boff, blen, eoff, efl, slots;
+    PoolBuf bbytes, bscan, boff, blen, eoff, efl, slots;
     EdState s;
     uint64_t* kmin = nullptr;   // nb each
     uint64_t* nloci = nullptr;

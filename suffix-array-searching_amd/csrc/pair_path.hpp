@@ -73,7 +73,7 @@ struct PairCall {
 // Steps 1..3: the batch, its loci and the join's slots.  The scratch lives as long as the state
 struct PairState {
     MapState ms;
-    MmPoolBuf pslots, meta, toff, lmin, lkey, ldist;
+    PoolBuf pslots, meta, toff, lmin, lkey, ldist;
 };
 
 // Steps 1..3.  All arrays on the device; Q: the caller's 2 np reads

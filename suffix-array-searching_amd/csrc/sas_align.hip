@@ -276,13 +276,12 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
                      uint16_t* out_runs, hipStream_t st, uint32_t flags, bool validate) {
     hipMemPool_t pool;
     TRY(sas_scratch_pool(x, &pool));
-    DevBuf bflag;  // a per-call flag word when it is read back (concurrent calls on other streams)
+    BadFlag bflag;  // armed when it is read back
     if (validate) {
-        TRY(bflag.alloc(4, "align flag"));
-        HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
+        TRY(bflag.arm(st));
         const uint64_t total = Q.qoff ? Q.nq : Q.nq * (uint64_t)Q.m;
         hipLaunchKernelGGL(k_al_validate, dim3(tile_grid(grid_for(total))), dim3(256), 0, st, Q.qbytes, Q.qoff, Q.qlen,
-                           Q.nq, total, bflag.as<uint32_t>());
+                           Q.nq, total, bflag.ptr());
         HIP_TRY(hipGetLastError());
     }
     uint64_t blocks = (na + AL_T - 1) / AL_T;
@@ -293,7 +292,7 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
     const uint32_t wbytes = kb == 1 ? 1u : (kb == 3 ? 2u : (kb == 7 ? 4u : 8u));
     // direction words: one per row of the longest query that is served, per thread of the grid
     const uint64_t rows = Q.qoff ? SAS_ED_MAX_M : std::min<uint64_t>(std::max<uint32_t>(Q.m, 1u), SAS_ED_MAX_M);
-    MmPoolBuf scr;
+    PoolBuf scr;
     TRY(scr.alloc(pool, blocks * AL_BLOCK * rows * wbytes, st));
     AlArgs a{};
     a.tw = x->text_w;
@@ -318,8 +317,7 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
     HIP_TRY(hipGetLastError());
     if (validate) {
         uint32_t hbad = 0;
-        HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        TRY(bflag.read(st, &hbad));
         if (hbad) SAS_FAIL(EINVAL, std::string(fn) + ": query bytes must be DNA codes 0..3");
     }
     return 0;

@@ -322,7 +322,7 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     HIP_TRY(hipGetLastError());
     TRY(timer.stop(&ed_last_verify_ms));
     // proposals: one per accepted end of every candidate
-    TRY(mm_scan(pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
+    TRY(pool_scan(pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
                 s.pscan.as<uint64_t>(), C + 1));
     HIP_TRY(hipMemcpyAsync(&s.P, s.pscan.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -344,13 +344,13 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     {
         size_t tbytes = 0;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
-        MmPoolBuf tmp;
+        PoolBuf tmp;
         TRY(tmp.alloc(pool, tbytes, st));
         HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tbytes, kdb, vdb, (size_t)P, 0, kbits, st));
     }
     s.skeys = kdb.current();
     s.svals = vdb.current();
-    TRY(mm_scan(pool, st,
+    TRY(pool_scan(pool, st,
                 rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), EdFirst{s.skeys, P}),
                 s.uscan.as<uint64_t>(), P + 1));
     hipLaunchKernelGGL(k_ed_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, s.skeys, s.uscan.as<uint64_t>(), P, nq,

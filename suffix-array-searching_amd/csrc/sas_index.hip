@@ -1,7 +1,10 @@
-// sas_index.hip -- what every unit needs of a built index: the library's error state, freeing
-// an index, its stats, and copying its arrays out (SA, LCP, substrings of the packed text).
+// sas_index.hip -- what every unit needs of a built index: the library's error state, its
+// scratch pool (sas_scratch_pool), freeing an index, its stats, and copying its arrays out
+// (SA, LCP, substrings of the packed text).
 #include "build_util.hpp"
 #include "build_steps.hpp"
+
+#include <mutex>
 
 // ------------------------------------------------------------------ error state
 static thread_local std::string g_err = "ok";
@@ -16,7 +19,29 @@ int sas_errno_of(hipError_t e) {
 }
 extern "C" const char* sas_last_error(void) { return g_err.c_str(); }
 
-// ------------------------------------------------------------------ free, stats
+// ------------------------------------------------------------------ scratch pool, free, stats
+// The scratch of an exact (variable-size) sharded step comes from a stream-ordered pool
+// owned by the index (created on first use, destroyed by sas_free).  Its release threshold
+// of "never" keeps freed blocks for the next step; the device's default pool, which other
+// libraries in the process share, is left alone.
+int sas_scratch_pool(const sas_index* x, hipMemPool_t* out) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> g(mu);
+    if (!x->scratch_pool) {
+        hipMemPoolProps pp{};
+        pp.allocType = hipMemAllocationTypePinned;
+        pp.location.type = hipMemLocationTypeDevice;
+        pp.location.id = x->device;
+        hipMemPool_t pool = nullptr;
+        HIP_TRY(hipMemPoolCreate(&pool, &pp));
+        uint64_t thr = UINT64_MAX;
+        HIP_TRY(hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr));
+        x->scratch_pool = pool;
+    }
+    *out = x->scratch_pool;
+    return 0;
+}
+
 void free_index(sas_index* x) {
     if (!x) return;
     void* ptrs[] = {x->text_w, x->sa, x->lcp, x->llcp, x->prefix, x->stree, x->rel, x->scratch,
@@ -24,10 +49,10 @@ void free_index(sas_index* x) {
                      x->tag_first, x->text2_base, x->lay_dev};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     sas_stage_pool_free(x->stage);
-    if (x->route_pool) {  // its blocks were freed stream-ordered: drain before destroying
+    if (x->scratch_pool) {  // its blocks were freed stream-ordered: drain before destroying
         (void)hipSetDevice(x->device);
         (void)hipDeviceSynchronize();
-        (void)hipMemPoolDestroy(x->route_pool);
+        (void)hipMemPoolDestroy(x->scratch_pool);
     }
     delete x;
 }

@@ -17,7 +17,7 @@
 //                   index: three u64 arrays in one device allocation (layout.hpp);
 //   sas_translate   k_translate: text position (and span) -> (sequence id, offset), or
 //                   SAS_SEQ_NONE when the interval is not inside one segment.
-#include "build_util.hpp"
+#include "call_io.hpp"
 #include "layout_host.hpp"
 
 #include <algorithm>
@@ -211,24 +211,21 @@ extern "C" int sas_translate(const sas_index* x, const void* pos, const uint32_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t w = u32 ? 4 : 8;
     const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
-    DevBuf dpos, dspan, dseq, doff;
+    DevBuf dpos, dspan;
+    HostOutputs ho;
     const void* kpos = pos;
     const uint32_t* kspan = span_or_null;
     uint32_t* kseq = out_seq;
     void* koff = out_off;
     if (!dev) {  // host arrays: copy in, run, copy out (synchronous)
-        TRY(dpos.alloc(count * w, "translate positions"));
-        TRY(dseq.alloc(count * 4, "translate sequence ids"));
-        TRY(doff.alloc(count * w, "translate offsets"));
-        HIP_TRY(hipMemcpyAsync(dpos.p, pos, count * w, hipMemcpyHostToDevice, st));
+        TRY(host_copy_in(dpos, pos, count * w, "translate positions"));
+        kpos = dpos.p;
         if (span_or_null) {
-            TRY(dspan.alloc(count * 4, "translate spans"));
-            HIP_TRY(hipMemcpyAsync(dspan.p, span_or_null, count * 4, hipMemcpyHostToDevice, st));
+            TRY(host_copy_in(dspan, span_or_null, count * 4, "translate spans"));
             kspan = dspan.as<uint32_t>();
         }
-        kpos = dpos.p;
-        kseq = dseq.as<uint32_t>();
-        koff = doff.p;
+        TRY(ho.twin(out_seq, count * 4, "translate sequence ids", &kseq));
+        TRY(ho.twin(out_off, count * w, "translate offsets", &koff));
     }
     const bool staged = layout_words(x->lay.nseq, x->lay.nseg) <= TR_LDS_WORDS;
     const dim3 grid(tile_grid(std::min(grid_for(count, TR_BLOCK), (unsigned)x->num_cus * 8)));
@@ -241,8 +238,7 @@ extern "C" int sas_translate(const sas_index* x, const void* pos, const uint32_t
     }
     HIP_TRY(hipGetLastError());
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out_seq, kseq, count * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_off, koff, count * w, hipMemcpyDeviceToHost, st));
+        TRY(ho.copy_back(st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
@@ -267,17 +263,16 @@ extern "C" int sas_kmer_keys(const uint8_t* text, uint64_t n, uint32_t k, uint64
     *count = cnt;
     if (cnt == 0 || !out) return 0;
     bool dev = flags & SAS_DEVICE_PTRS;
-    void *dt = nullptr, *dout = nullptr;
-    struct Free { void** p; ~Free() { if (*p) (void)hipFree(*p); } } f1{&dt}, f2{&dout};
+    DevBuf dt, dout;
     const uint8_t* tptr = text;
     uint32_t* optr = out;
     uint64_t tb = cnt + k - 1;
     if (!dev) {
-        HIP_TRY(hipMalloc(&dt, tb + 64));
-        HIP_TRY(hipMemcpy(dt, text, tb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&dout, cnt * 4));
-        tptr = static_cast<const uint8_t*>(dt);
-        optr = static_cast<uint32_t*>(dout);
+        TRY(dt.alloc(tb + 64, "k-mer text"));  // the packer reads whole words past the end
+        HIP_TRY(hipMemcpy(dt.p, text, tb, hipMemcpyHostToDevice));
+        tptr = dt.as<uint8_t>();
+        TRY(dout.alloc(cnt * 4, "k-mer keys"));
+        optr = dout.as<uint32_t>();
     }
     uint64_t blocks = (cnt + 255) / 256;
     if (blocks > 262144) blocks = 262144;

@@ -27,10 +27,8 @@
 //
 // SAS_BUILD_TAG_LINES has no SA array: a rank is looked up through tl_sa_at (common.hpp), a
 // binary search over the buckets' first ranks per element.  That path is correct, not tuned.
-#include "build_util.hpp"
+#include "call_io.hpp"
 #include "csr_tile.hpp"
-
-#include <rocprim/device/device_scan.hpp>
 
 #include <type_traits>
 #include <vector>
@@ -244,16 +242,7 @@ extern "C" int sas_locate_offsets(const sas_index* x, const uint64_t* lo, const 
     hipLaunchKernelGGL(k_locate_count, dim3((unsigned)blocks), dim3(LOC_BLOCK), 0, st, lo, hi, nq, x->rank_lo, x->sa_n,
                        max_per_query, out_off);
     HIP_TRY(hipGetLastError());
-    size_t tbytes = 0;
-    void* tmp = nullptr;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, out_off, out_off, (uint64_t)0, (size_t)(nq + 1),
-                                    rocprim::plus<uint64_t>(), st));
-    HIP_TRY(hipMallocFromPoolAsync(&tmp, tbytes ? tbytes : 8, pool, st));
-    hipError_t e = rocprim::exclusive_scan(tmp, tbytes, out_off, out_off, (uint64_t)0, (size_t)(nq + 1),
-                                           rocprim::plus<uint64_t>(), st);
-    HIP_TRY(hipFreeAsync(tmp, st));
-    HIP_TRY(e);
-    return 0;
+    return pool_scan(pool, st, out_off, out_off, nq + 1);
 }
 
 template <class SA>
@@ -279,13 +268,13 @@ extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uin
     const uint64_t ntiles = (capacity + LOC_T - 1) / LOC_T;
     // the partition pre-pass unless the caller turns it off (the measured choice: DESIGN.md)
     const bool partition = !(flags & SAS_LOCATE_NO_PARTITION);
+    PoolBuf tiles;
     LocTile* tile_q = nullptr;
     if (partition) {
         hipMemPool_t pool;
         TRY(sas_scratch_pool(x, &pool));
-        void* p = nullptr;
-        HIP_TRY(hipMallocFromPoolAsync(&p, (ntiles + 1) * sizeof(LocTile), pool, st));
-        tile_q = static_cast<LocTile*>(p);
+        TRY(tiles.alloc(pool, (ntiles + 1) * sizeof(LocTile), st));
+        tile_q = tiles.as<LocTile>();
         uint64_t pb = (ntiles + 1 + LOC_BLOCK - 1) / LOC_BLOCK;
         if (pb > (uint64_t)x->num_cus * LOC_BLOCKS_PER_CU) pb = (uint64_t)x->num_cus * LOC_BLOCKS_PER_CU;
         hipLaunchKernelGGL(k_locate_tiles, dim3((unsigned)pb), dim3(LOC_BLOCK), 0, st, lo, out_off, nq, ntiles, tile_q);
@@ -307,9 +296,7 @@ extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uin
         with_sa_w(x->sa_w, [&](auto W) {
             launch_fill(u32, grid, st, SaView<decltype(W)::value>{x->sa}, x, lo, out_off, nq, out_pos, capacity, tile_q, ntiles);
         });
-    hipError_t e = hipGetLastError();
-    if (tile_q) HIP_TRY(hipFreeAsync(tile_q, st));
-    HIP_TRY(e);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -329,9 +316,9 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
     if (flags & SAS_DEVICE_PTRS) {
         hipMemPool_t pool;
         TRY(sas_scratch_pool(x, &pool));
-        void* p = nullptr;
-        HIP_TRY(hipMallocFromPoolAsync(&p, (nq ? nq : 1) * 16, pool, st));
-        uint64_t* lo = static_cast<uint64_t*>(p);
+        PoolBuf lohi;
+        TRY(lohi.alloc(pool, nq * 16, st));
+        uint64_t* lo = lohi.as<uint64_t>();
         uint64_t* hi = lo + nq;
         int rc = ragged ? sas_search_range(x, qbytes, qoff, qlen, nq, lo, hi, stream, sflags)
                         : sas_search_range_fixed(x, qbytes, m_fixed, nq, lo, hi, stream, sflags);
@@ -341,24 +328,20 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
             rc = EIO;
             sas_set_error(rc, std::string(fn) + ": copy of the total failed");
         }
-        (void)hipFreeAsync(p, st);
         return rc;
     }
     // host arrays: ranges through the staged host pipeline, then one device result buffer
-    std::vector<uint64_t> hlo(nq ? nq : 1), hhi(nq ? nq : 1);
-    if (ragged) TRY(sas_search_range(x, qbytes, qoff, qlen, nq, hlo.data(), hhi.data(), stream, sflags));
-    else TRY(sas_search_range_fixed(x, qbytes, m_fixed, nq, hlo.data(), hhi.data(), stream, sflags));
-    DevBuf dr, doff, dpos;
-    TRY(dr.alloc((nq ? nq : 1) * 16, "locate ranges"));
-    TRY(doff.alloc((nq + 1) * 8, "locate offsets"));
+    std::vector<uint64_t> hr(nq ? 2 * nq : 1);  // lo, then hi: one buffer and one copy
+    if (ragged) TRY(sas_search_range(x, qbytes, qoff, qlen, nq, hr.data(), hr.data() + nq, stream, sflags));
+    else TRY(sas_search_range_fixed(x, qbytes, m_fixed, nq, hr.data(), hr.data() + nq, stream, sflags));
+    DevBuf dr;
+    HostOutputs ho;
+    TRY(host_copy_in(dr, hr.data(), nq * 16, "locate ranges"));
     uint64_t* lo = dr.as<uint64_t>();
-    uint64_t* hi = lo + nq;
-    if (nq) {
-        HIP_TRY(hipMemcpyAsync(lo, hlo.data(), nq * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(hi, hhi.data(), nq * 8, hipMemcpyHostToDevice, st));
-    }
-    TRY(sas_locate_offsets(x, lo, hi, nq, max_per_query, doff.as<uint64_t>(), stream, lflags));
-    HIP_TRY(hipMemcpyAsync(out_off, doff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    uint64_t* doff;
+    TRY(ho.twin(out_off, (nq + 1) * 8, "locate offsets", &doff));
+    TRY(sas_locate_offsets(x, lo, lo + nq, nq, max_per_query, doff, stream, lflags));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t total = out_off[nq];
     if (out_total) *out_total = total;
@@ -366,9 +349,10 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
         SAS_FAIL(ENOSPC, std::string(fn) + ": " + std::to_string(total) + " positions, capacity " +
                              std::to_string(capacity) + " (size out_pos from *out_total and call again)");
     if (total == 0) return 0;
-    TRY(dpos.alloc(total * esz, "locate positions"));
-    TRY(sas_locate_fill(x, lo, doff.as<uint64_t>(), nq, dpos.p, total, stream, lflags));
-    HIP_TRY(hipMemcpyAsync(out_pos, dpos.p, total * esz, hipMemcpyDeviceToHost, st));
+    void* dpos;
+    TRY(ho.twin(out_pos, total * esz, "locate positions", &dpos));
+    TRY(sas_locate_fill(x, lo, doff, nq, dpos, total, stream, lflags));
+    TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -5,7 +5,7 @@
 //
 //   1. the batch      forward only: the caller's queries as they are.  Otherwise one scratch batch
 //                     of the participating strands, forward as query i and reverse as query nq + i
-//                     (reverse alone: query i): k_map_revcomp_fixed, or for ragged queries mm_scan
+//                     (reverse alone: query i): k_map_revcomp_fixed, or for ragged queries pool_scan
 //                     over qlen, k_map_layout (offsets and lengths of the batch) and k_map_fill
 //                     (output-centric over the batch's bytes: a workgroup owns a tile of output
 //                     bytes and finds each one's query with al_tile_queries);
@@ -238,7 +238,7 @@ int map_select_batch(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_
         B.nq = nb;
         if (Q.qoff) {
             TRY(ms.bscan.alloc(pool, (nq + 1) * 8, st));
-            TRY(mm_scan(pool, st,
+            TRY(pool_scan(pool, st,
                         rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0),
                                                          MapLenAt{Q.qlen, nq}),
                         ms.bscan.as<uint64_t>(), nq + 1));
@@ -374,7 +374,7 @@ static int map_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     TRY(map_select_batch(x, Q, k, max_seed_hits, strands, st, flags, ms));
     const MmQueries& B = ms.B;
     // 4. the records and the alignment request
-    MmPoolBuf areq;
+    PoolBuf areq;
     const bool align = o.start || o.nruns || o.runs;
     const bool u32 = (flags & SAS_LOCATE_U32) != 0;
     const uint64_t esz = u32 ? 4 : 8;
@@ -474,29 +474,25 @@ static int revcomp_device(const char* fn, const uint8_t* q, const uint64_t* qoff
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const unsigned cap_grid = (unsigned)std::max(cus, 1) * 8;
-    DevBuf bflag;  // a per-call flag word when it is read back
-    if (validate) {
-        TRY(bflag.alloc(4, "revcomp flag"));
-        HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    }
+    BadFlag bflag;  // armed when it is read back
+    if (validate) TRY(bflag.arm(st));
     if (qoff) {
         hipMemPool_t pool;
         HIP_TRY(hipDeviceGetDefaultMemPool(&pool, dev));
-        TRY(mm_scan(pool, st,
+        TRY(pool_scan(pool, st,
                     rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), MapLenAt{qlen, nq}),
                     out_off, nq + 1));
         // the grid does not wait for the byte total: the tiles are strided over it
         hipLaunchKernelGGL(k_map_fill, dim3(tile_grid(cap_grid)), dim3(AL_BLOCK), 0, st, q, qoff, qlen,
-                           nq, out_off, nq, (uint64_t)0, out, bflag.as<uint32_t>());
+                           nq, out_off, nq, (uint64_t)0, out, bflag.ptr());
     } else {
         hipLaunchKernelGGL(k_map_revcomp_fixed, dim3(tile_grid(std::min(grid_for(nq * (uint64_t)m), cap_grid))),
-                           dim3(256), 0, st, q, m, nq, out, bflag.as<uint32_t>());
+                           dim3(256), 0, st, q, m, nq, out, bflag.ptr());
     }
     HIP_TRY(hipGetLastError());
     if (validate) {
         uint32_t hbad = 0;
-        HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        TRY(bflag.read(st, &hbad));
         if (hbad) SAS_FAIL(EINVAL, std::string(fn) + ": query bytes must be DNA codes 0..3");
     }
     return 0;

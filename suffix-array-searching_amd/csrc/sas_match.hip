@@ -186,17 +186,6 @@ static void launch_match_w(int qw, dim3 grid, hipStream_t st, const MatchArgs& a
 // the words past 128 chars from the bytes); an unknown longest query (0) gives 4
 static int match_qw(uint64_t maxlen) { return maxlen == 0 ? 4 : maxlen <= 32 ? 1 : maxlen <= 64 ? 2 : 4; }
 
-struct PoolBuf {  // stream-ordered scratch from the index's pool
-    void* p = nullptr;
-    hipStream_t st = nullptr;
-    ~PoolBuf() { if (p) (void)hipFreeAsync(p, st); }
-    int alloc(hipMemPool_t pool, size_t bytes, hipStream_t s) {
-        st = s;
-        HIP_TRY(hipMallocFromPoolAsync(&p, bytes ? bytes : 8, pool, s));
-        return 0;
-    }
-};
-
 // All arrays on the device.  maxlen: the batch's longest query when the host knows it, else 0
 static int match_device(const char* fn, const sas_index* x, int mode, const uint8_t* qbytes, const uint64_t* qoff,
                         const uint32_t* qlen, uint32_t m, uint64_t nq, uint64_t maxlen, bool validate,
@@ -211,11 +200,8 @@ static int match_device(const char* fn, const sas_index* x, int mode, const uint
         TRY(srange.alloc(pool, nq * 8, st));
         (out_lo ? out_hi : out_lo) = static_cast<uint64_t*>(srange.p);
     }
-    DevBuf bflag;  // a per-call flag word when it is read back (concurrent calls on other streams)
-    if (validate) {
-        TRY(bflag.alloc(4, "match flag"));
-        HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    }
+    BadFlag bflag;  // armed when it is read back
+    if (validate) TRY(bflag.arm(st));
     MatchArgs a{};
     a.tw = x->text_w;
     a.n = x->n;
@@ -232,11 +218,11 @@ static int match_device(const char* fn, const sas_index* x, int mode, const uint
     a.out_len = out_len;
     a.out_pos = out_pos;
     a.out_qoff = static_cast<uint64_t*>(sqoff.p);
-    a.bad = validate ? bflag.as<uint32_t>() : x->scratch;
+    a.bad = validate ? bflag.ptr() : x->scratch;
     if (validate) {
         const uint64_t total = mode == MATCH_FIXED ? nq * (uint64_t)m : nq;
         hipLaunchKernelGGL(k_match_validate, dim3(grid_for(mode == MATCH_RAGGED ? nq : total)), dim3(256), 0, st,
-                           qbytes, mode == MATCH_RAGGED ? qoff : nullptr, qlen, nq, total, bflag.as<uint32_t>());
+                           qbytes, mode == MATCH_RAGGED ? qoff : nullptr, qlen, nq, total, bflag.ptr());
     }
     uint64_t blocks = (nq + MATCH_BLOCK - 1) / MATCH_BLOCK;
     const uint64_t capb = (uint64_t)x->num_cus * MATCH_BPC;
@@ -254,8 +240,7 @@ static int match_device(const char* fn, const sas_index* x, int mode, const uint
     }
     if (validate) {
         uint32_t hbad = 0;
-        HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        TRY(bflag.read(st, &hbad));
         if (hbad) SAS_FAIL(EINVAL, std::string(fn) + ": query bytes must be DNA codes 0..3");
     }
     return 0;

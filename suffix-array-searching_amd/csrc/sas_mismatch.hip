@@ -216,7 +216,7 @@ extern "C" double sas_locate_mismatch_verify_ms(uint64_t* candidates) {
 // Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
 struct MmState {
     SeedState seed;
-    MmPoolBuf woff, qw, verdict, cpos, scan;
+    PoolBuf woff, qw, verdict, cpos, scan;
     uint64_t C = 0;
 };
 
@@ -237,7 +237,7 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         TRY(s.woff.alloc(pool, (nq + 1) * 8, st));
         hipLaunchKernelGGL(k_mm_wcount, seed_grid(x, nq + 1), dim3(256), 0, st, Q, s.woff.as<uint64_t>());
         HIP_TRY(hipGetLastError());
-        TRY(mm_scan(pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
+        TRY(pool_scan(pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
         if (Q.qoff) HIP_TRY(hipMemcpyAsync(&words, s.woff.as<uint64_t>() + nq, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipMemcpyAsync(&s.C, coff + np, 8, hipMemcpyDeviceToHost, st));
@@ -286,7 +286,7 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     else mm_launch_verify<false>(x, pre, vgrid, st, a);
     HIP_TRY(hipGetLastError());
     TRY(timer.stop(&mm_last_verify_ms));
-    TRY(mm_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
+    TRY(pool_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
                 s.scan.as<uint64_t>(), C + 1));
     hipLaunchKernelGGL(k_mm_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, coff, s.scan.as<uint64_t>(), nq, kp1,
                        out_off, out_total);

@@ -453,7 +453,7 @@ int pair_join_batch(const sas_index* x, const MmQueries& Q, const PairCall& c, h
     const MmQueries& B = ms.B;
     const EdState& s = ms.s;
     // the pairs' slots and the loci scratch, sized from P (the locus total stays on the device)
-    MmPoolBuf &pslots = ps.pslots, &meta = ps.meta, &toff = ps.toff, &lmin = ps.lmin, &lkey = ps.lkey,
+    PoolBuf &pslots = ps.pslots, &meta = ps.meta, &toff = ps.toff, &lmin = ps.lmin, &lkey = ps.lkey,
               &ldist = ps.ldist;
     TRY(pslots.alloc(pool, 3 * np * 8, st));
     HIP_TRY(hipMemsetAsync(pslots.p, 0xFF, np * 8, st));
@@ -483,7 +483,7 @@ int pair_join_batch(const sas_index* x, const MmQueries& Q, const PairCall& c, h
         a.nfwd = nq;
         hipLaunchKernelGGL(k_pair_heads, tgrid, dim3(MAP_BLOCK), 0, st, a);
         HIP_TRY(hipGetLastError());
-        TRY(mm_scan(pool, st, a.toff, a.toff, tiles + 1));
+        TRY(pool_scan(pool, st, a.toff, a.toff, tiles + 1));
         hipLaunchKernelGGL(k_pair_loci, tgrid, dim3(MAP_BLOCK), 0, st, a);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_pair_meta, dim3(1), dim3(64), 0, st, a);
@@ -524,8 +524,8 @@ int pair_finish(const sas_index* x, const PairCall& c, PairState& ps, const uint
     const uint64_t nq = B.nq / 2, np = nq / 2;
     hipMemPool_t pool;
     TRY(sas_scratch_pool(x, &pool));
-    MmPoolBuf &pslots = ps.pslots, &meta = ps.meta, &lkey = ps.lkey, &ldist = ps.ldist;
-    MmPoolBuf areq;
+    PoolBuf &pslots = ps.pslots, &meta = ps.meta, &lkey = ps.lkey, &ldist = ps.ldist;
+    PoolBuf areq;
     // 4. the records and the alignment request
     const bool align = o.start || o.nruns || o.runs;
     const bool u32 = (flags & SAS_LOCATE_U32) != 0;

@@ -259,7 +259,7 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
     PairState ps;
     TRY(pair_join_batch(x, Q, c, st, flags, ps));
     const uint64_t nq = Q.nq, np = nq / 2, P = ps.ms.s.P;
-    MmPoolBuf rslots, ascan, aidx;
+    PoolBuf rslots, ascan, aidx;
     uint64_t* rmin = nullptr;
     uint64_t* rcnt = nullptr;
     if (c.max_anchors && P) {  // without a proposal there is no locus and no anchor
@@ -287,7 +287,7 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
         an.k_rescue = c.k_rescue;
         an.max_anchors = c.max_anchors;
         // 3a. the anchors
-        TRY(mm_scan(pool, st, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), an),
+        TRY(pool_scan(pool, st, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), an),
                     ascan.as<uint64_t>(), P + 1));
         hipLaunchKernelGGL(k_rescue_anchors, seed_grid(x, P), dim3(256), 0, st, an, ascan.as<uint64_t>(), P,
                            aidx.as<uint64_t>());

@@ -1,12 +1,9 @@
-// sas_route.hip -- the sharded step's send and receive sides: sas_route(_batch), sas_route_pack(_cap),
-// sas_shard_gather and the index's scratch pool (sas_scratch_pool).
-#include "build_util.hpp"
+// sas_route.hip -- the sharded step's send and receive sides: sas_route(_batch), sas_route_pack(_cap)
+// and sas_shard_gather.
+#include "call_io.hpp"
 #include "search_args.hpp"
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <cstdlib>
-#include <mutex>
 
 // ------------------------------------------------------------------ sharded-mode routing
 // Routing compares a query with the splitter suffixes by their first 32 chars (staged in
@@ -62,44 +59,26 @@ static int route_impl(const sas_index* x, const uint64_t* splitter_pos, uint32_t
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     bool dev = flags & SAS_DEVICE_PTRS;
-    DeviceBuf bsp, bq, bout, boff, blen;
+    DevBuf bsp;
+    HostQueries hq;
+    HostOutputs ho;
     const uint64_t* dsp = splitter_pos;
-    const uint8_t* dq = qbytes;
-    const uint64_t* doff = qoff;
-    const uint32_t* dlen = qlen;
+    MmQueries Q{qbytes, qoff, qlen, m, nq};
     uint32_t* dout = out_shard;
-    if (!dev) {
-        uint64_t span = nq * (uint64_t)m;
-        if (qoff) {
-            span = 0;
-            for (uint64_t k = 0; k < nq; k++) span = qoff[k] + qlen[k] > span ? qoff[k] + qlen[k] : span;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMalloc(&bsp.p, nsplit * 8 + 8));
-        if (nsplit) HIP_TRY(hipMemcpy(bsp.p, splitter_pos, nsplit * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&bq.p, span + 64));
-        if (span) HIP_TRY(hipMemcpy(bq.p, qbytes, span, hipMemcpyHostToDevice));
-        if (qoff) {
-            HIP_TRY(hipMalloc(&boff.p, nq * 8));
-            HIP_TRY(hipMalloc(&blen.p, nq * 4));
-            HIP_TRY(hipMemcpy(boff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(blen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-            doff = static_cast<const uint64_t*>(boff.p);
-            dlen = static_cast<const uint32_t*>(blen.p);
-        }
-        HIP_TRY(hipMalloc(&bout.p, nq * 4));
-        dsp = static_cast<const uint64_t*>(bsp.p);
-        dq = static_cast<const uint8_t*>(bq.p);
-        dout = static_cast<uint32_t*>(bout.p);
+    if (!dev) {  // host arrays: copy in, the kernel, copy out (synchronous; bytes not validated)
+        TRY(host_copy_in(bsp, splitter_pos, nsplit * 8, "route splitters"));
+        dsp = bsp.as<uint64_t>();
+        TRY(hq.stage("route", qbytes, qoff != nullptr, qoff, qlen, m, nq, st, &Q));
+        TRY(ho.twin(out_shard, nq * 4, "route shards", &dout));
     }
     uint64_t blocks = (nq + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_route, dim3((unsigned)blocks), dim3(256), 0, st, x->text_w, x->n, dsp, nsplit, dq, m, doff,
-                       dlen, nq, dout, x->scratch);
+    hipLaunchKernelGGL(k_route, dim3((unsigned)blocks), dim3(256), 0, st, x->text_w, x->n, dsp, nsplit, Q.qbytes, m,
+                       Q.qoff, Q.qlen, nq, dout, x->scratch);
     HIP_TRY(hipGetLastError());
     if (!dev) {
+        TRY(ho.copy_back(st));
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(out_shard, dout, nq * 4, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -320,28 +299,6 @@ __global__ void k_pack_totals(const uint64_t* __restrict__ base_slot, uint32_t W
     }
 }
 
-// The scratch of an exact (variable-size) sharded step comes from a stream-ordered pool
-// owned by the index (created on first use, destroyed by sas_free).  Its release threshold
-// of "never" keeps freed blocks for the next step; the device's default pool, which other
-// libraries in the process share, is left alone.
-int sas_scratch_pool(const sas_index* x, hipMemPool_t* out) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> g(mu);
-    if (!x->route_pool) {
-        hipMemPoolProps pp{};
-        pp.allocType = hipMemAllocationTypePinned;
-        pp.location.type = hipMemLocationTypeDevice;
-        pp.location.id = x->device;
-        hipMemPool_t pool = nullptr;
-        HIP_TRY(hipMemPoolCreate(&pool, &pp));
-        uint64_t thr = UINT64_MAX;
-        HIP_TRY(hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr));
-        x->route_pool = pool;
-    }
-    *out = x->route_pool;
-    return 0;
-}
-
 static int route_pack_impl(const sas_index* x, const uint64_t* splitter_pos, uint32_t nsplit,
                            const uint8_t* qbytes, uint32_t m, uint64_t nq, uint64_t cap, uint64_t* out_counts,
                            uint8_t* out_send, uint64_t* out_slot, void* stream, uint32_t flags) {
@@ -390,36 +347,23 @@ static int route_pack_impl(const sas_index* x, const uint64_t* splitter_pos, uin
     // with splitters the routing reads each query anyway and packs it on the way (words);
     // without (one part) the routing reads nothing and the scatter packs from the bytes
     const bool pack_in_route = packed && nsplit > 0;
-    void* dest = nullptr;
-    void* cnt = nullptr;
-    void* tmp = nullptr;
-    void* words = nullptr;
-    size_t tbytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0,
-                                    (size_t)(nblk * W), rocprim::plus<uint64_t>(), st));
-    HIP_TRY(hipMallocFromPoolAsync(&dest, nq * 4, pool, st));
-    HIP_TRY(hipMallocFromPoolAsync(&cnt, nblk * W * 8, pool, st));
-    HIP_TRY(hipMallocFromPoolAsync(&tmp, tbytes ? tbytes : 8, pool, st));
-    if (pack_in_route) HIP_TRY(hipMallocFromPoolAsync(&words, nq * 8, pool, st));
+    PoolBuf dest, cnt, words;
+    TRY(dest.alloc(pool, nq * 4, st));
+    TRY(cnt.alloc(pool, nblk * W * 8, st));
+    if (pack_in_route) TRY(words.alloc(pool, nq * 8, st));
     if (pack_in_route)
         hipLaunchKernelGGL(k_route_count<true>, dim3((unsigned)nblk), dim3(PACK_BLOCK), 0, st, x->text_w, x->n,
-                           splitter_pos, nsplit, qbytes, m, nq, nblk, static_cast<uint64_t*>(cnt),
-                           static_cast<uint32_t*>(dest), static_cast<uint64_t*>(words));
+                           splitter_pos, nsplit, qbytes, m, nq, nblk, cnt.as<uint64_t>(), dest.as<uint32_t>(),
+                           words.as<uint64_t>());
     else
         hipLaunchKernelGGL(k_route_count<false>, dim3((unsigned)nblk), dim3(PACK_BLOCK), 0, st, x->text_w, x->n,
-                           splitter_pos, nsplit, qbytes, m, nq, nblk, static_cast<uint64_t*>(cnt),
-                           static_cast<uint32_t*>(dest), (uint64_t*)nullptr);
-    HIP_TRY(rocprim::exclusive_scan(tmp, tbytes, static_cast<uint64_t*>(cnt), static_cast<uint64_t*>(cnt),
-                                    (uint64_t)0, (size_t)(nblk * W), rocprim::plus<uint64_t>(), st));
-    hipLaunchKernelGGL(k_pack_scatter, dim3((unsigned)nblk), dim3(PACK_BLOCK), 0, st, static_cast<uint32_t*>(dest),
-                       nq, W, nblk, static_cast<uint64_t*>(cnt), qbytes, m, out_send, out_slot, cap, packed,
-                       static_cast<const uint64_t*>(words));
-    hipLaunchKernelGGL(k_pack_totals, dim3(1), dim3(256), 0, st, static_cast<uint64_t*>(cnt), W, nblk, nq, out_counts);
+                           splitter_pos, nsplit, qbytes, m, nq, nblk, cnt.as<uint64_t>(), dest.as<uint32_t>(),
+                           (uint64_t*)nullptr);
+    TRY(pool_scan(pool, st, cnt.as<uint64_t>(), cnt.as<uint64_t>(), nblk * W));
+    hipLaunchKernelGGL(k_pack_scatter, dim3((unsigned)nblk), dim3(PACK_BLOCK), 0, st, dest.as<uint32_t>(), nq, W, nblk,
+                       cnt.as<uint64_t>(), qbytes, m, out_send, out_slot, cap, packed, words.as<const uint64_t>());
+    hipLaunchKernelGGL(k_pack_totals, dim3(1), dim3(256), 0, st, cnt.as<uint64_t>(), W, nblk, nq, out_counts);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipFreeAsync(dest, st));
-    HIP_TRY(hipFreeAsync(cnt, st));
-    HIP_TRY(hipFreeAsync(tmp, st));
-    if (words) HIP_TRY(hipFreeAsync(words, st));
     return 0;
 }
 

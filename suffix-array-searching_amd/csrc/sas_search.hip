@@ -32,7 +32,7 @@
 // _quad_llcp / _prefix / _tagged .hip, over search_args.hpp, search_keys.hpp and search_quad.hpp); this
 // unit holds the host dispatch (launch_search, launch_range), the host-pointer staging pipeline and the
 // C entry points.  The sharded step's routing and packing are in sas_route.hip.
-#include "build_util.hpp"
+#include "call_io.hpp"
 #include "host_stage.hpp"
 #include "search_args.hpp"
 
@@ -405,12 +405,13 @@ static bool fits_stage(uint32_t m_fixed, const uint32_t* qlen, uint64_t nq) {
 }
 
 // A direct call: device pointers, or host arrays with a query longer than a staging chunk.
-// Such host arrays stage through plain hipMalloc + synchronous copies: the stream-ordered
-// allocator + pageable async copies raced on the null stream.
+// Such host arrays take the synchronous host-pointer path of call_io.hpp (HostQueries,
+// HostOutputs), not the stream-ordered allocator.
 // begin() wires a's query, bad-code and output pointers (dev_out[0] is a.out_pos), sets the
 // batch's query words (qw, a.m_max) and launches the validation.  After the caller's kernels,
-// end() synchronises if anything is read back, copies host outputs out and fails with
-// "<what>: query bytes must be DNA codes 0..3" on an invalid code.
+// end() copies host outputs out, synchronises if anything is read back and fails with
+// "<what>: query bytes must be DNA codes 0..3" on an invalid code: the caller's arrays are
+// filled even then.
 struct DirectIo {  // the caller's arrays, host or device
     const uint8_t* qbytes;
     const uint64_t* qoff;  // null: fixed length a.m_fixed
@@ -421,87 +422,57 @@ struct DirectIo {  // the caller's arrays, host or device
 };
 
 struct DirectCall {
-    DirectIo io{};
     int qw = 4;
     bool dev = false, check_bad = false;
     uint64_t* dev_out[2] = {};
-    DeviceBuf bflag, bqb, bqoff, bqlen, bout[2], bprobes;
+    BadFlag bflag;
+    HostQueries hq;
+    HostOutputs ho;
 
     // a.nq and a.m_fixed are set
-    int begin(const sas_index* x, hipStream_t st, uint32_t flags, SearchArgs& a, const DirectIo& caller) {
-        io = caller;
+    int begin(const sas_index* x, hipStream_t st, uint32_t flags, SearchArgs& a, const DirectIo& io) {
         dev = (flags & SAS_DEVICE_PTRS) != 0;
         const bool ragged = io.qoff != nullptr;
-        const uint8_t* qbytes = io.qbytes;
-        const uint64_t* qoff = io.qoff;
-        const uint32_t* qlen = io.qlen;
         const uint64_t nq = a.nq;
         // invalid-code flag: a per-call word when it is read back, so that concurrent calls
         // on other streams (allowed: the index is immutable) never see each other's flags;
         // otherwise the index's write-only sink (fill_args)
         check_bad = !dev || (flags & SAS_VALIDATE);
         if (check_bad) {
-            HIP_TRY(hipMalloc(&bflag.p, 4));
-            HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-            a.bad = static_cast<uint32_t*>(bflag.p);
+            TRY(bflag.arm(st));
+            a.bad = bflag.ptr();
         }
         if (dev) {  // ragged: the longest query is unknown
             qw = ragged ? 4 : qw_for(a.m_fixed);
             a.m_max = ragged ? 0 : a.m_fixed;
-            a.qbytes = qbytes;
-            a.qoff = qoff;
-            a.qlen = qlen;
+            a.qbytes = io.qbytes;
+            a.qoff = io.qoff;
+            a.qlen = io.qlen;
             dev_out[0] = io.out[0];
             dev_out[1] = io.out[1];
             a.out_probes = io.probes;
         } else {
-            uint64_t span = nq * (uint64_t)a.m_fixed, maxlen = a.m_fixed;
-            if (ragged) {
-                span = maxlen = 0;
-                for (uint64_t k = 0; k < nq; k++) {
-                    uint64_t e = qoff[k] + qlen[k];
-                    if (e > span) span = e;
-                    if (qlen[k] > maxlen) maxlen = qlen[k];
-                }
-            }
+            const uint32_t maxlen = ragged ? *std::max_element(io.qlen, io.qlen + nq) : a.m_fixed;
             qw = qw_for(maxlen);
-            a.m_max = maxlen ? (uint32_t)maxlen : 1;
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMalloc(&bqb.p, span + 64));
-            if (span) HIP_TRY(hipMemcpy(bqb.p, qbytes, span, hipMemcpyHostToDevice));
-            a.qbytes = static_cast<const uint8_t*>(bqb.p);
-            if (ragged) {
-                HIP_TRY(hipMalloc(&bqoff.p, nq * 8));
-                HIP_TRY(hipMalloc(&bqlen.p, nq * 4));
-                HIP_TRY(hipMemcpy(bqoff.p, qoff, nq * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(bqlen.p, qlen, nq * 4, hipMemcpyHostToDevice));
-                a.qoff = static_cast<const uint64_t*>(bqoff.p);
-                a.qlen = static_cast<const uint32_t*>(bqlen.p);
-            }
-            for (int i = 0; i < io.nout; i++) {
-                HIP_TRY(hipMalloc(&bout[i].p, nq * 8));
-                dev_out[i] = static_cast<uint64_t*>(bout[i].p);
-            }
-            if (io.probes) {
-                HIP_TRY(hipMalloc(&bprobes.p, nq * 4));
-                a.out_probes = static_cast<uint32_t*>(bprobes.p);
-            }
+            a.m_max = maxlen ? maxlen : 1;
+            MmQueries Q;
+            TRY(hq.stage("search", io.qbytes, ragged, io.qoff, io.qlen, a.m_fixed, nq, st, &Q));
+            a.qbytes = Q.qbytes;
+            a.qoff = Q.qoff;
+            a.qlen = Q.qlen;
+            for (int i = 0; i < io.nout; i++) TRY(ho.twin(io.out[i], nq * 8, "search positions", &dev_out[i]));
+            TRY(ho.twin(io.probes, nq * 4, "search probes", &a.out_probes));
         }
         a.out_pos = dev_out[0];
         if (check_bad) launch_validate(st, a, nq);  // every query byte, not only those a kernel packs
         return 0;
     }
 
-    int end(hipStream_t st, const SearchArgs& a, const char* what) {
-        if (!check_bad && dev) return 0;
-        HIP_TRY(hipStreamSynchronize(st));
+    int end(hipStream_t st, const char* what) {
+        if (!check_bad) return 0;
+        TRY(ho.copy_back(st));
         uint32_t hbad = 0;
-        if (check_bad) HIP_TRY(hipMemcpy(&hbad, a.bad, 4, hipMemcpyDeviceToHost));
-        if (!dev) {
-            for (int i = 0; i < io.nout; i++)
-                HIP_TRY(hipMemcpy(io.out[i], dev_out[i], a.nq * 8, hipMemcpyDeviceToHost));
-            if (io.probes) HIP_TRY(hipMemcpy(io.probes, a.out_probes, a.nq * 4, hipMemcpyDeviceToHost));
-        }
+        TRY(bflag.read(st, &hbad));
         if (hbad) SAS_FAIL(EINVAL, std::string(what) + ": query bytes must be DNA codes 0..3");
         return 0;
     }
@@ -530,13 +501,11 @@ static int slices_impl(const sas_index* x, const uint64_t* qoff, const uint32_t*
     a.out_probes = out_probes;
     // every slice inside the text: checked first, always (an out-of-range slice would read
     // past the packed text); the call synchronises to read the flag back
-    DeviceBuf bflag;
-    HIP_TRY(hipMalloc(&bflag.p, 4));
-    HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    launch(launch_ctx(nq, 256, 65536, st), k_validate_slices, qoff, qlen, nq, x->n, static_cast<uint32_t*>(bflag.p));
+    BadFlag bflag;
+    TRY(bflag.arm(st));
+    launch(launch_ctx(nq, 256, 65536, st), k_validate_slices, qoff, qlen, nq, x->n, bflag.ptr());
     uint32_t hbad = 0;
-    HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(bflag.read(st, &hbad));
     if (hbad) SAS_FAIL(EINVAL, "SAS_QUERIES_ARE_SLICES: a slice reaches past the text");
     return launch_search(x, a, algo, 4, flags, st);
 }
@@ -566,7 +535,7 @@ static int search_impl(const sas_index* x, const uint8_t* qbytes, const uint64_t
     DirectCall call;
     TRY(call.begin(x, st, flags, a, {qbytes, qoff, qlen, 1, {out_pos, nullptr}, out_probes}));
     TRY(launch_search(x, a, algo, call.qw, flags, st));
-    return call.end(st, a, "search");
+    return call.end(st, "search");
 }
 
 extern "C" int sas_search_batch(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff,
@@ -605,14 +574,12 @@ extern "C" int sas_pack_queries(const uint8_t* qbytes, uint32_t m, uint64_t nq, 
         return 0;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    DeviceBuf bflag;
-    HIP_TRY(hipMalloc(&bflag.p, 4));
-    HIP_TRY(hipMemsetAsync(bflag.p, 0, 4, st));
-    launch(launch_ctx(nq, 256, 65536, st), k_pack_queries, qbytes, m, nq, out_words, static_cast<uint32_t*>(bflag.p));
+    BadFlag bflag;
+    TRY(bflag.arm(st));
+    launch(launch_ctx(nq, 256, 65536, st), k_pack_queries, qbytes, m, nq, out_words, bflag.ptr());
     HIP_TRY(hipGetLastError());
     uint32_t hbad = 0;
-    HIP_TRY(hipMemcpyAsync(&hbad, bflag.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(bflag.read(st, &hbad));
     if (hbad) SAS_FAIL(EINVAL, "sas_pack_queries: query bytes must be DNA codes 0..3");
     return 0;
 }
@@ -722,7 +689,7 @@ static int range_impl(const sas_index* x, const uint8_t* qbytes, uint32_t m_fixe
     TRY(call.begin(x, st, flags, a, {qbytes, ragged ? qoff : nullptr, qlen, 2, {out_lo, out_hi}, nullptr}));
     launch_range(x, a, call.qw, flags, st, call.dev_out[1]);
     HIP_TRY(hipGetLastError());
-    return call.end(st, a, "sas_search_range");
+    return call.end(st, "sas_search_range");
 }
 
 extern "C" int sas_search_range(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,

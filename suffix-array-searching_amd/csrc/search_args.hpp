@@ -197,8 +197,3 @@ void launch_prefix_range(const LaunchCtx& c, const SearchArgs& a, bool inline_sl
                          int qw, uint64_t* dhi);
 void launch_tagged(int num_cus, hipStream_t st, const SearchArgs& a, int qw, bool slices);
 void launch_tagged_range(const LaunchCtx& c, const SearchArgs& a, int qw, uint64_t* dhi);
-
-struct DeviceBuf {
-    void* p = nullptr;
-    ~DeviceBuf() { if (p) (void)hipFree(p); }
-};

@@ -1,6 +1,6 @@
 // seed_verify.hip -- the stages that every seed-and-verify call runs, defined once
-// (seed_verify.hpp declares them): the index preconditions, the seed stage up to the candidate
-// offsets, and the host-pointer path (queries in, outputs back).
+// (seed_verify.hpp declares them): the index preconditions and the seed stage up to the
+// candidate offsets.
 #include "seed_verify.hpp"
 
 static_assert(SAS_MM_TRUNCATED == SAS_ED_TRUNCATED && SAS_MM_SHORT == SAS_ED_SHORT,
@@ -81,47 +81,4 @@ int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t
                        s.skip.as<uint16_t>(), qflags);
     HIP_TRY(hipGetLastError());
     return sas_locate_offsets(x, s.lo, s.hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS);
-}
-
-int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& what) {
-    TRY(d.alloc(bytes, what.c_str()));
-    if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-
-int HostQueries::stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                       const uint32_t* qlen, uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q) {
-    const std::string l(label);
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
-        span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
-    }
-    TRY(dq.alloc(span + 64, (l + " queries").c_str()));  // the packers read whole words past the end
-    HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(host_copy_in(dqoff, qoff, nq * 8, l + " query offsets"));
-        TRY(host_copy_in(dqlen, qlen, nq * 4, l + " query lengths"));
-    }
-    *Q = MmQueries{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
-    return 0;
-}
-
-int HostOutputs::twin_bytes(void* h, size_t nbytes, const char* what, void** d) {
-    *d = nullptr;
-    if (!h) return 0;
-    if (count == MAX) SAS_FAIL(EINVAL, std::string("HostOutputs: more than ") + std::to_string(MAX) + " outputs");
-    TRY(dev[count].alloc(nbytes, what));
-    host[count] = h;
-    bytes[count] = nbytes;
-    *d = dev[count++].p;
-    return 0;
-}
-
-int HostOutputs::copy_back(hipStream_t st) {
-    for (; copied < count; copied++)
-        if (bytes[copied])
-            HIP_TRY(hipMemcpyAsync(host[copied], dev[copied].p, bytes[copied], hipMemcpyDeviceToHost, st));
-    return 0;
 }

@@ -1,23 +1,18 @@
 // seed_verify.hpp -- what the seed-and-verify calls share (sas_mismatch.hip: Hamming distance,
 // sas_edit.hip: edit distance, and the calls built on them: sas_align.hip, sas_map.hip,
-// sas_pairs.hip, sas_rescue.hip; sas_match.hip takes the host-side helpers):
+// sas_pairs.hip, sas_rescue.hip; sas_match.hip takes the index preconditions), over the call
+// scaffolding of call_io.hpp (scratch, scan, the host-pointer path, the query batch MmQueries):
 //
-//   * device code that the kernels of those files inline: the query batch as the kernels see it,
-//     the cut of a query into k + 1 pieces, and the output-centric tiling (csr_tile.hpp) of the
-//     candidates (one candidate = one occurrence of one piece) and of the elements of a CSR list
-//     (sas_align.hip: alignments, sas_map.hip: the bytes of a ragged batch);
-//   * stream-ordered scratch, a scan helper, the grid of the helper kernels and an event pair
-//     for the *_TIMING knobs;
+//   * device code that the kernels of those files inline: the cut of a query into k + 1 pieces,
+//     and the output-centric tiling (csr_tile.hpp) of the candidates (one candidate = one
+//     occurrence of one piece) and of the elements of a CSR list (sas_align.hip: alignments,
+//     sas_map.hip: the bytes of a ragged batch);
+//   * the grid of the helper kernels and an event pair for the *_TIMING knobs;
 //   * declared here and defined once in seed_verify.hip: the index preconditions
-//     (seed_index_checks), the seed stage up to the candidate offsets (seed_candidates) and the
-//     host-pointer path of every call (HostQueries, HostOutputs).
+//     (seed_index_checks) and the seed stage up to the candidate offsets (seed_candidates).
 #pragma once
-#include "build_util.hpp"
+#include "call_io.hpp"
 #include "csr_tile.hpp"
-
-#include <rocprim/device/device_scan.hpp>
-
-#include <algorithm>
 
 #define MM_BLOCK 256
 #define MM_T 2048          // candidates per tile
@@ -25,16 +20,6 @@
 #define MM_SLICE 4096      // candidate offsets of a tile staged in LDS (16 KiB)
 #define MM_MAX_GRID (1u << 20)
 #define MM_MAX_K 15
-
-struct MmQueries {
-    const uint8_t* qbytes;
-    const uint64_t* qoff;  // null: fixed-length queries of m chars
-    const uint32_t* qlen;
-    uint32_t m;
-    uint64_t nq;
-    __device__ __forceinline__ uint64_t off(uint64_t q) const { return qoff ? qoff[q] : q * (uint64_t)m; }
-    __device__ __forceinline__ uint32_t len(uint64_t q) const { return qoff ? qlen[q] : m; }
-};
 
 // b_j: the first char of piece j of a query of m chars cut into kp1 pieces
 __device__ __forceinline__ uint32_t mm_piece_start(uint32_t j, uint32_t m, uint32_t kp1) {
@@ -76,31 +61,6 @@ __device__ __forceinline__ void al_tile_queries(const uint64_t* __restrict__ off
                                                 uint32_t (&ok)[AL_PER]) {
     csr_tile_owners<AL_T, AL_SLICE, AL_BLOCK>(off, nq, t0, n_el, rel, sh_p, qi, ok,
                                               [&](int, uint64_t c, uint64_t q) { return csr_in_bounds(off, q, c); });
-}
-
-struct MmPoolBuf {  // stream-ordered scratch from the index's pool
-    void* p = nullptr;
-    hipStream_t st = nullptr;
-    ~MmPoolBuf() { if (p) (void)hipFreeAsync(p, st); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-    int alloc(hipMemPool_t pool, size_t bytes, hipStream_t s) {
-        st = s;
-        HIP_TRY(hipMallocFromPoolAsync(&p, bytes ? bytes : 8, pool, s));
-        return 0;
-    }
-};
-
-// out[i] = sum of in[0 .. i) over `count` elements of an iterator of u64 (out may be in)
-template <class In>
-static int mm_scan(hipMemPool_t pool, hipStream_t st, In in, uint64_t* out, uint64_t count) {
-    size_t tbytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tbytes, in, out, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
-                                    st));
-    MmPoolBuf tmp;
-    TRY(tmp.alloc(pool, tbytes, st));
-    HIP_TRY(rocprim::exclusive_scan(tmp.p, tbytes, in, out, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(),
-                                    st));
-    return 0;
 }
 
 // The grid of a helper kernel of 256 threads that strides over `count` elements: at most 8
@@ -151,7 +111,7 @@ int seed_index_checks(const std::string& w, const sas_index* x, uint32_t k, uint
 // reads the candidate total coff[np] back when it needs it)
 struct SeedState {
     hipMemPool_t pool = nullptr;
-    MmPoolBuf poff, plen, lohi, coff, qfl, skip;
+    PoolBuf poff, plen, lohi, coff, qfl, skip;
     uint64_t* lo = nullptr;  // np each
     uint64_t* hi = nullptr;
 };
@@ -161,35 +121,3 @@ struct SeedState {
 // be null): the per-query flags, SAS_MM_* = SAS_ED_*.  No host read
 int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t max_m,
                     bool skip_mask, uint8_t* qflags, hipStream_t st, uint32_t flags, SeedState& s);
-
-// src[0 .. bytes) of the host in a device buffer of its own (synchronous)
-int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& what);
-
-// The host-pointer path's way in: the queries of a call on the device.  The bytes copied are
-// those up to the largest qoff + qlen, not their sum: ragged queries may overlap
-struct HostQueries {
-    DevBuf dq, dqoff, dqlen;
-    // Waits for `st`, then copies (synchronous).  label: the call's word in "<label> queries"
-    int stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff, const uint32_t* qlen,
-              uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q);
-};
-
-// The host-pointer path's way out: the device twins of a call's host outputs.  twin() allocates
-// one for a host pointer that is not null and hands out the device pointer (null for null);
-// copy_back() queues the copies to the host of every twin made since the last copy_back()
-struct HostOutputs {
-    static const int MAX = 16;
-    DevBuf dev[MAX];
-    void* host[MAX];
-    size_t bytes[MAX];
-    int count = 0, copied = 0;
-    int twin_bytes(void* h, size_t nbytes, const char* what, void** d);
-    template <class T>
-    int twin(T* h, size_t nbytes, const char* what, T** d) {
-        void* p = nullptr;
-        TRY(twin_bytes(h, nbytes, what, &p));
-        *d = static_cast<T*>(p);
-        return 0;
-    }
-    int copy_back(hipStream_t st);
-};

@@ -6,6 +6,7 @@ the oracle elsewhere) for batches that span many chunks, fixed and ragged, every
 (bytes, packed on the host, the caller's packed words); a code > 3 anywhere fails the whole
 call with EINVAL; concurrent host calls on one index each get their own slots.
 """
+import errno
 import threading
 
 import numpy as np
@@ -155,3 +156,51 @@ def test_ranges_host_pipeline(env):
     bad[777 * m + 5] = 9
     with pytest.raises(sas.SasError):
         idx.search_range_fixed(bad, m)
+
+
+def test_direct_host_path_long_query():
+    """One query longer than a staging chunk (SAS_STAGE_BYTES = 16 MiB) takes the direct host
+    path of sas_search_* / sas_search_range*: host arrays in, device twins, copy back.  Equal
+    to the same call on CUDA tensors; a code > 3 is EINVAL after the outputs were written."""
+    import torch
+
+    import sas_amd
+    from sas_amd._lib import SasError
+    n, m = (16 << 20) + 4096, (16 << 20) + 1
+    t = sas_amd.random_string(n, seed=78)
+    idx = sas_amd.SaNaive.build(torch.from_numpy(t).cuda(), lcp=False, stree=False, quad=False, llcp=False,
+                                prefix=False)
+    q0 = t[1000:1000 + m].copy()
+    q1 = q0.copy()
+    q1[-1] = (q1[-1] + 1) & 3
+    qb = np.concatenate([q0, q1])
+    dqb = torch.from_numpy(qb).cuda()
+
+    pos, pr = idx.search_fixed(qb, m, algo="plain", probes=True)
+    dpos, dpr = idx.search_fixed(dqb, m, algo="plain", probes=True)
+    torch.cuda.synchronize()
+    dpos = dpos.cpu().numpy().astype(np.uint64)
+    assert np.array_equal(pos, dpos)
+    assert np.array_equal(pr, dpr.cpu().numpy().astype(np.uint32))
+    assert pos[0] == 1000  # a 16 M-char prefix of a random text is unique: the lower bound is that suffix
+
+    lo, hi = idx.search_range_fixed(qb, m)
+    dlo, dhi = idx.search_range_fixed(dqb, m)
+    assert np.array_equal(lo, dlo.cpu().numpy().astype(np.uint64))
+    assert np.array_equal(hi, dhi.cpu().numpy().astype(np.uint64))
+    assert hi[0] - lo[0] == 1
+
+    qoff, qlen = np.array([0, m], np.uint64), np.array([m, 5], np.uint32)
+    got = idx.search_batch(qb, qoff, qlen, algo="plain")
+    d = idx.search_batch(dqb, torch.from_numpy(qoff.view(np.int64)).cuda(),
+                         torch.from_numpy(qlen.view(np.int32)).cuda(), algo="plain")
+    assert np.array_equal(got, d.cpu().numpy().astype(np.uint64))
+
+    bad = qb.copy()
+    bad[m - 1] = 4
+    sentinel = np.uint64(0xFFFFFFFFFFFFFFFF)
+    out = np.full(2, sentinel, np.uint64)
+    with pytest.raises(SasError, match="DNA codes") as e:
+        idx.search_fixed(bad, m, algo="plain", out=out)
+    assert e.value.code == errno.EINVAL
+    assert (out != sentinel).all() and out[1] == dpos[1]  # q1 is valid: its answer is there

@@ -1069,6 +1069,43 @@ def test_route_pack(sas):
     assert np.array_equal(send.reshape(nq, m)[slot], qb.reshape(nq, m))
 
 
+def test_route_batch(sas):
+    """sas_route_batch (ragged queries), host arrays == device arrays == sas_route on the same
+    bytes as fixed-length queries."""
+    import torch
+    from sas_amd import _lib
+    n, m, nq = 1 << 16, 20, 1000
+    t = sas.random_string(n, seed=62)
+    idx = sas.SaNaive.build(t, lcp=False, stree=False)
+    sa = idx.suffix_array()
+    splitters = np.array([sa[n // 4], sa[n // 2], sa[3 * n // 4]], np.uint64)
+    rng = np.random.default_rng(4)
+    qb = np.concatenate([t[o:o + m] for o in rng.integers(0, n - m, nq)])
+    expect = idx.route(splitters, qb, m)
+    assert len(np.unique(expect)) == 4  # every shard is met
+    # ragged layout: the queries in another order, 3 bytes of gap after each
+    perm = rng.permutation(nq)
+    off = np.empty(nq, np.uint64)
+    off[perm] = np.arange(nq, dtype=np.uint64) * (m + 3)
+    buf = np.full(nq * (m + 3) + 64, 3, np.uint8)
+    for k in range(nq):
+        buf[int(off[k]):int(off[k]) + m] = qb[k * m:(k + 1) * m]
+    lens = np.full(nq, m, np.uint32)
+    L = _lib.lib()
+    host = np.full(nq, 99, np.uint32)
+    _lib.check(L.sas_route_batch(idx._h, splitters.ctypes.data, 3, buf.ctypes.data, off.ctypes.data, lens.ctypes.data,
+                                 nq, host.ctypes.data, None, 0))
+    dsp, dbuf = torch.from_numpy(splitters.view(np.int64)).cuda(), torch.from_numpy(buf).cuda()
+    doff, dlen = torch.from_numpy(off.view(np.int64)).cuda(), torch.from_numpy(lens.view(np.int32)).cuda()
+    dout = torch.full((nq,), 99, dtype=torch.int32, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(L.sas_route_batch(idx._h, dsp.data_ptr(), 3, dbuf.data_ptr(), doff.data_ptr(), dlen.data_ptr(), nq,
+                                 dout.data_ptr(), st, _lib.SAS_DEVICE_PTRS))
+    torch.cuda.synchronize()
+    assert np.array_equal(host, expect)
+    assert np.array_equal(dout.cpu().numpy().astype(np.uint32), expect)
+
+
 def test_full_size_algorithms_agree_and_are_lower_bounds(sas):
     """BASELINE size (n = 2^30, 10^6 mixed queries: positive len 32 as in the bench,
     random negatives, other lengths), index as the bench builds it (p = 16 two-suffix
