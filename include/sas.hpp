@@ -25,6 +25,10 @@
  * Error behaviour: the reference panics with panic = "abort" (Cargo.toml:12).  Here a
  * non-zero status throws sas::Panic (a std::runtime_error carrying sas_last_error()); left
  * uncaught it terminates the process as the reference's panic does.
+ *
+ * Every batched call takes an empty batch: no kernel runs and the result vectors are empty, the
+ * CSR offsets being {0} (sas.h: nq == 0 writes out_off[0] = 0 and nothing else); stride is still
+ * set.  tests/cpp/test_calls.cpp runs each of them against recorded answers.
  */
 #ifndef SAS_HPP
 #define SAS_HPP
@@ -227,7 +231,8 @@ class SaNaive {
 
     /* search_prefix for any number of queries in one call (sas_locate: range search, offsets
      * and the ragged expansion on the GPU, one copy back); max_per_query caps each query's
-     * positions (0: no cap) */
+     * positions at its first max_per_query in SA order (0: no cap).  locate({}) is off = {0} and no
+     * position */
     Located locate(const std::vector<Seq>& qs, uint64_t max_per_query = 0) const {
         std::vector<uint8_t> bytes;
         std::vector<uint64_t> qoff(qs.size());
@@ -611,17 +616,24 @@ inline double bench_batch(const SaNaive& sa, const std::vector<Seq>& queries, co
     return s;
 }
 
-/* the script of alignment a of an Aligned as a string such as "17=1X14=": = a match, X a
- * substitution, I a query char that the text lacks, D a text char that the query lacks */
-inline std::string cigar(const SaNaive::Aligned& r, size_t a) {
+/* the script in runs[a * stride .. a * stride + nruns[a]) as a string such as "17=1X14=" */
+inline std::string cigar(const std::vector<uint16_t>& runs, const std::vector<uint8_t>& nruns, size_t stride, size_t a) {
     std::string s;
-    for (size_t i = 0; i < r.nruns[a]; i++) {
-        const uint16_t run = r.runs[a * r.stride + i];
+    for (size_t i = 0; i < nruns[a]; i++) {
+        const uint16_t run = runs[a * stride + i];
         s += std::to_string(run >> 2);
         s += "=XID"[run & 3u];
     }
     return s;
 }
+
+/* the script of alignment a of an Aligned as a string such as "17=1X14=": = a match, X a
+ * substitution, I a query char that the text lacks, D a text char that the query lacks */
+inline std::string cigar(const SaNaive::Aligned& r, size_t a) { return cigar(r.runs, r.nruns, r.stride, a); }
+
+/* the script of read a of a Mapped, MappedPairs or MappedPairsRescue, against the strand it was
+ * placed on ("" for an unmapped read) */
+inline std::string cigar(const SaNaive::Mapped& r, size_t a) { return cigar(r.runs, r.nruns, r.stride, a); }
 
 /* random_string (sas/util.rs:9-15) with ChaCha8Rng::seed_from_u64(seed) */
 inline std::vector<uint8_t> random_string(size_t n, uint64_t seed = 31415) {
