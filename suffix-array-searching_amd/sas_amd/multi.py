@@ -11,7 +11,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .sa import _as_u8, _prefix_flags, _ptr, _quad_flags
+from ._io import HOST, as_u8 as _as_u8, ptr as _ptr
+from .sa import _build_flags
 
 MODES = {"replicate": _lib.SAS_MULTI_REPLICATE, "shard": _lib.SAS_MULTI_SHARD}
 
@@ -31,8 +32,7 @@ class SaMulti:
         prefix: the prefix table for algo="prefix" (as SaNaive.build)."""
         t = np.ascontiguousarray(_as_u8(t))
         dv = np.ascontiguousarray(devices, np.int32)
-        flags |= (_lib.SAS_BUILD_LCP if lcp else 0) | (_lib.SAS_BUILD_STREE if stree else 0)
-        flags |= (_lib.SAS_BUILD_SECTOR if sector else 0) | _quad_flags(quad) | _prefix_flags(prefix, quad, len(t))
+        flags = _build_flags(len(t), flags, lcp=lcp, stree=stree, sector=sector, quad=quad, llcp=False, prefix=prefix)
         h = C.c_void_p()
         check(lib().sas_build_multi(_ptr(t), len(t), _ptr(dv), len(dv), MODES[mode], flags, C.byref(h)))
         return cls(h, len(t), dv.tolist(), mode)
@@ -51,10 +51,10 @@ class SaMulti:
         qbytes = np.ascontiguousarray(_as_u8(qbytes))
         qoff = np.ascontiguousarray(qoff, np.uint64)
         qlen = np.ascontiguousarray(qlen, np.uint32)
-        out = np.zeros(max(len(qoff), 1), np.uint64)
+        out = HOST.new("u64", len(qoff))
         check(lib().sas_search_multi(self._h, _ptr(qbytes), _ptr(qoff), _ptr(qlen), len(qoff), _lib.ALGOS[algo],
                                      _ptr(out), 0))
-        return out[:len(qoff)]
+        return out
 
     def free(self):
         if self._h:

@@ -17,13 +17,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._io import HOST, Side, is_cuda as _is_cuda, ptr as _ptr
 from ._lib import SasError, check, lib
 
 MAX = 0x7FFFFFFF  # sst/node.rs:5
-
-
-def _is_cuda(x) -> bool:
-    return hasattr(x, "is_cuda") and bool(x.is_cuda)
 
 
 class _Index:
@@ -63,34 +60,29 @@ class _Index:
 
     def nodes(self) -> np.ndarray:
         words = self.size() // 4
-        out = np.zeros(max(words, 1), np.uint32)
-        check(lib().sst_copy_nodes(self._h, out.ctypes.data, words))
-        return out[:words]
+        out = HOST.new("u32", words)
+        check(lib().sst_copy_nodes(self._h, _ptr(out), words))
+        return out
 
     def query(self, qs, want_rank: bool = False, stream=None, flags: int = 0, out=None):
         """out: (device queries only) a caller-owned 4-byte result tensor of at least qs.numel()
         elements, contiguous, on qs's device; host queries refuse it (they return a new array)."""
-        if _is_cuda(qs):
-            import torch
-            if out is None:
-                out = torch.empty(qs.numel(), dtype=torch.int32, device=qs.device)
-            elif not (_is_cuda(out) and out.device == qs.device and out.element_size() == 4 and
-                      out.is_contiguous() and out.numel() >= qs.numel()):
+        side = Side(qs, stream)
+        if side.dev:
+            if out is not None and not (_is_cuda(out) and out.device == qs.device and out.element_size() == 4 and
+                                        out.is_contiguous() and out.numel() >= qs.numel()):
                 raise SasError(22, "sst query: out must be a contiguous 4-byte tensor on the queries' device "
                                    f"with >= {qs.numel()} elements")
-            rank = torch.empty(qs.numel(), dtype=torch.int64, device=qs.device) if want_rank else None
-            st = stream if stream is not None else torch.cuda.current_stream(qs.device).cuda_stream
-            check(lib().sst_query(self._h, qs.data_ptr(), qs.numel(), out.data_ptr(),
-                                  rank.data_ptr() if want_rank else None, st, flags | _lib.SST_DEVICE_PTRS))
-            return (out, rank) if want_rank else out
-        if out is not None:
+        elif out is not None:
             raise SasError(22, "sst query: out= is for device queries; host queries return a new array")
-        qs = np.ascontiguousarray(qs, np.uint32)
-        out = np.zeros(max(len(qs), 1), np.uint32)
-        rank = np.zeros(max(len(qs), 1), np.uint64) if want_rank else None
-        check(lib().sst_query(self._h, qs.ctypes.data, len(qs), out.ctypes.data,
-                              rank.ctypes.data if want_rank else None, stream, flags))
-        return (out[: len(qs)], rank[: len(qs)]) if want_rank else out[: len(qs)]
+        else:
+            qs = np.ascontiguousarray(qs, np.uint32)
+        nq = side.count(qs)
+        out = side.new("u32", nq) if out is None else out
+        rank = side.new("u64" if want_rank else None, nq)
+        check(lib().sst_query(self._h, _ptr(qs), nq, _ptr(out), _ptr(rank), side.stream,
+                              flags | (_lib.SST_DEVICE_PTRS if side.dev else 0)))
+        return (out, rank) if want_rank else out
 
     def query_one(self, q: int) -> int:
         return int(self.query(np.array([q], np.uint32))[0])

@@ -113,6 +113,66 @@ def test_flag_and_algo_mirror_matches_header():
     assert _lib.SAS_BUILD_PREFIX_P(17) == 17 << 16
 
 
+def _header_prototypes():
+    """name -> (return type, [parameter declarations]) of every function include/sas.h and
+    include/sst.h declare, comments stripped."""
+    import re
+    protos = {}
+    for h in _lib.HEADERS:
+        src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S))
+        for ret, name, params in re.findall(
+                r"^\s*((?:const\s+)?[a-z_0-9]+\s*\*?)\s*\b((?:sas|sst)_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+            params = " ".join(params.split())
+            protos[name] = (" ".join(ret.split()), [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return protos
+
+
+def _c_class(decl: str):
+    """The ctypes class of one C parameter or return type: "ptr" for any pointer."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.replace("const", " ").split()]
+    base = words[0] if words else ""
+    known = {"uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "int": C.c_int, "double": C.c_double}
+    if base.startswith(("sas_", "sst_", "enum")):  # an enum passed by value
+        return C.c_int
+    return known.get(base, f"no ctypes class for `{decl}`")
+
+
+def _ctypes_class(t):
+    if t is None:
+        return None
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    return t
+
+
+def test_argtypes_match_the_header_prototypes():
+    """Every function the headers declare has, in _lib.lib(), argtypes of the prototype's length with
+    the prototype's class at every position (any pointer: c_void_p, c_char_p or a POINTER; uint64_t,
+    uint32_t, int / enum and double: their ctypes twins), and every non-int return type its restype.
+    A wrong width passes every host test and corrupts a call on the GPU."""
+    protos = _header_prototypes()
+    assert sorted(protos) == _lib.declared_symbols() and len(protos) >= 70
+    L = _lib.lib()
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(L, name)
+        want = [_c_class(p) for p in params]
+        if fn.argtypes is None:
+            if params:
+                bad.append(f"{name}: no argtypes for ({', '.join(params)})")
+        else:
+            got = [_ctypes_class(t) for t in fn.argtypes]
+            if len(got) != len(want):
+                bad.append(f"{name}: {len(got)} argtypes, the header declares {len(want)} parameters")
+            bad += [f"{name}: parameter {i} `{p}` is bound as {getattr(g, '__name__', g)}"
+                    for i, (p, g, w) in enumerate(zip(params, got, want)) if g != w]
+        if _c_class(ret) != _ctypes_class(fn.restype):
+            bad.append(f"{name}: returns `{ret}`, restype is {getattr(fn.restype, '__name__', fn.restype)}")
+    assert not bad, "\n".join(bad)
+
+
 def test_stats_struct_matches_header():
     """ctypes SasStats lists the fields of sas_stats in include/sas.h, in order."""
     import re
