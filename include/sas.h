@@ -639,9 +639,73 @@ int sas_locate_edit_fixed(const sas_index* index, const uint8_t* qbytes, uint32_
  * figures in ms (< 0: none), with the candidates verified and the ends proposed. */
 double sas_locate_edit_verify_ms(uint64_t* candidates);
 double sas_locate_edit_dedup_ms(uint64_t* proposals);
+/* Maximal exact matches (MEMs) of every query, by seed and extend: the first step for a query
+ * that shares only stretches with the text (a long read, a contig, another assembly; MUMmer's
+ * -maxmatch).  For a query p of m chars, the text t of n chars and min_len = L >= 1, a match is a
+ * triple (i, j, len) with len >= L, i + len <= m, j + len <= n and p[i .. i + len) = t[j .. j +
+ * len).  It is maximal when both hold:
+ *   - left:  i = 0, or j = 0, or p[i - 1] != t[j - 1];
+ *   - right: i + len = m, or j + len = n, or p[i + len] != t[j + len].
+ * Nothing behind the text end takes part: the zero padding of the packed text is code 0 = 'A' and
+ * never extends a match.  Equivalently, the MEMs are the maximal runs of `true` of length >= L on
+ * the diagonals of the m x n matrix [p[i] = t[j]].
+ * Every MEM starts with an occurrence of the window p[i .. i + L), so the windows of all query
+ * offsets i <= m - L go through one sas_search_range, and one kernel takes every occurrence of
+ * every window: it drops those that extend to the left (one text char, one query byte) and
+ * extends the others to the right, 32 chars a step.  There is no bound on m other than u32.
+ *   - max_hits: if it is not 0, a query offset i whose window occurs more than max_hits times in
+ *     the text (its whole SA range) is skipped and the query flagged SAS_MEM_TRUNCATED; its
+ *     answer is exactly the MEMs (i, j, len) whose offset i was not skipped.  0: no limit;
+ *   - a query with m < L (the empty one included) gets no result and SAS_MEM_SHORT;
+ *   - SAS_MEM_UNIQUE (a call flag): only MEMs whose string t[j .. j + len) occurs exactly once in
+ *     the indexed text are reported (MUMmer's -mumreference).  It is decided from the SA
+ *     neighbours of the occurrence's rank r, text against text: unique iff lcp(t[SA[r - 1] ..],
+ *     t[j ..]) < len and lcp(t[SA[r + 1] ..], t[j ..]) < len, the lcps capped at the text end, a
+ *     neighbour that does not exist counting as smaller.  No LCP array is needed;
+ *   - with a sequence layout set (sas_set_layout) each segment is a text of its own, as for the
+ *     approximate calls: an occurrence [j, j + L) that does not lie inside one segment is no
+ *     candidate, and in both maximality rules the segment's lo and hi take the place of 0 and n.
+ *     max_hits and SAS_MEM_UNIQUE keep counting occurrences in the whole indexed text.  Without a
+ *     layout the call runs a kernel without these tests; a layout of one segment [0, n) gives
+ *     the same bytes;
+ *   - the reverse-complement strand is not searched: pass sas_revcomp's output as a second batch.
+ * Results in CSR form, as sas_locate_mismatch gives them: out_off[0..nq] (u64) and per match
+ * out_qpos (u32: i), out_tpos (u64, or u32 with SAS_LOCATE_U32, which needs n < 2^32: EINVAL
+ * otherwise: j) and out_len (u32); out_qflags is one byte per query (SAS_MEM_*; may be NULL).
+ * Inside a query the matches are ordered by ascending i, then by ascending SA rank of the suffix
+ * t[j ..].  min_len == 0 is EINVAL (checked before the index).  Flags: SAS_DEVICE_PTRS,
+ * SAS_LOCATE_U32, SAS_VALIDATE, SAS_NO_PREFIX_TABLE, SAS_MEM_UNIQUE.  Needs what sas_search_range
+ * needs (its error is returned otherwise) on a whole index (no shard, no part) with a u32 or
+ * packed 40-bit SA array; SAS_BUILD_TAGGED / SAS_BUILD_TAG_LINES indexes return ENOTSUP.
+ * With host pointers: synchronous, bytes always validated (those of short queries too);
+ * *out_total is always set, out_off and out_qflags always filled; if the total exceeds
+ * `capacity` nothing is copied to out_qpos / out_tpos / out_len and the call returns ENOSPC
+ * (all three NULL, capacity == 0 is the sizing call).  With SAS_DEVICE_PTRS: scratch from the
+ * index's stream-ordered pool (36 B per window and 24 B per candidate; a ragged batch 8 B per
+ * window more); nothing at or past `capacity` is written; out_total (device, may be NULL) =
+ * out_off[nq], which the caller checks against `capacity` afterwards.  nq == 0 writes
+ * out_off[0] = 0.  sas_mems_fixed synchronises on `stream` ONCE, to read the number of
+ * candidates (the occurrences of all windows that were not skipped) back to the host: it sizes
+ * the candidate scratch and the grid.  sas_mems synchronises once more before that, to read the
+ * number of windows of its ragged batch.  Nothing else synchronises unless SAS_VALIDATE is set. */
+#define SAS_MEM_TRUNCATED 1u /* out_qflags: a query offset was skipped (more than max_hits hits) */
+#define SAS_MEM_SHORT     2u /* out_qflags: m < min_len, no result                                */
+#define SAS_MEM_UNIQUE    (1u << 1) /* sas_mems*: only matches whose string occurs once in the text */
+int sas_mems(const sas_index* index, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen, uint64_t nq,
+             uint32_t min_len, uint64_t max_hits, uint64_t* out_off, uint32_t* out_qpos, void* out_tpos,
+             uint32_t* out_len, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
+             uint32_t flags);
+/* sas_mems for fixed-length queries qbytes[k*m .. (k+1)*m). */
+int sas_mems_fixed(const sas_index* index, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t min_len,
+                   uint64_t max_hits, uint64_t* out_off, uint32_t* out_qpos, void* out_tpos, uint32_t* out_len,
+                   uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags);
+/* Timing helper for benches: with SAS_MEM_TIMING=1 in the environment every sas_mems* call times
+ * its verify kernel with HIP events (and synchronises to do so); this returns the calling
+ * thread's last figure in ms (< 0: none) and the candidates it verified. */
+double sas_mems_verify_ms(uint64_t* candidates);
 /* Debug helper for tests: SAS_TILE_GRID=g in the environment (read at every call) caps at g
  * workgroups the grids of the tiled kernels of sas_locate*, sas_locate_mismatch*,
- * sas_locate_edit*, sas_align_edit*, sas_map_edit*, sas_map_pairs*, sas_map_pairs_rescue* and
+ * sas_locate_edit*, sas_mems*, sas_align_edit*, sas_map_edit*, sas_map_pairs*, sas_map_pairs_rescue* and
  * sas_revcomp*, so a small batch takes the tile loops of a large one; results do not depend on
  * it.  It only lowers a grid.  This returns the cap in force, 0 for none (unset, empty or not positive). */
 uint32_t sas_tile_grid_cap(void);

@@ -329,6 +329,46 @@ class SaNaive {
         return r;
     }
 
+    /* CSR result of mems: query k's maximal exact matches are the entries off[k] .. off[k+1]),
+     * query[qpos .. qpos + len) = text[tpos .. tpos + len), ordered by (qpos, SA rank of tpos);
+     * qflags[k] is a mask of SAS_MEM_TRUNCATED and SAS_MEM_SHORT */
+    struct Mems {
+        std::vector<uint64_t> off, tpos;
+        std::vector<uint32_t> qpos, len;
+        std::vector<uint8_t> qflags;
+    };
+
+    /* every maximal exact match of at least min_len chars of every query, in one call (sas_mems:
+     * seed and extend on the GPU); a query offset whose first min_len chars occur more than
+     * max_hits times is skipped (0: no limit); flags: SAS_MEM_UNIQUE keeps the matches whose
+     * string occurs once in the text */
+    Mems mems(const std::vector<Seq>& qs, uint32_t min_len, uint64_t max_hits = 0, uint32_t flags = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> qoff(qs.size());
+        std::vector<uint32_t> len(qs.size());
+        for (size_t i = 0; i < qs.size(); i++) {
+            qoff[i] = bytes.size();
+            len[i] = (uint32_t)qs[i].len;
+            bytes.insert(bytes.end(), qs[i].ptr, qs[i].ptr + qs[i].len);
+        }
+        bytes.resize(bytes.size() + 64, 0);
+        Mems r;
+        r.off.assign(qs.size() + 1, 0);
+        r.qflags.assign(qs.size(), 0);
+        uint64_t total = 0;
+        /* the sizing call (ENOSPC unless nothing matches), then the real one */
+        const int rc = sas_mems(h_, bytes.data(), qoff.data(), len.data(), qs.size(), min_len, max_hits, r.off.data(),
+                                nullptr, nullptr, nullptr, r.qflags.data(), 0, &total, nullptr, flags);
+        if (rc != ENOSPC) check(rc);
+        r.qpos.resize(total);
+        r.tpos.resize(total);
+        r.len.resize(total);
+        if (total)
+            check(sas_mems(h_, bytes.data(), qoff.data(), len.data(), qs.size(), min_len, max_hits, r.off.data(),
+                           r.qpos.data(), r.tpos.data(), r.len.data(), r.qflags.data(), total, &total, nullptr, flags));
+        return r;
+    }
+
     /* CSR result of locate_edit: query k's end positions are end[off[k] .. off[k+1]), ascending,
      * with D(e) (the least edit distance of the query to a text substring ending at e) in dist;
      * qflags[k] is a mask of SAS_ED_TRUNCATED, SAS_ED_SHORT and SAS_ED_LONG */

@@ -56,29 +56,42 @@ __global__ void k_seed_gate(MmQueries Q, uint32_t kp1, uint64_t max_seed_hits, u
     }
 }
 
-int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t max_m,
-                    bool skip_mask, uint8_t* qflags, hipStream_t st, uint32_t flags, SeedState& s) {
-    const uint32_t kp1 = k + 1;
-    const uint64_t nq = Q.nq, np = nq * kp1;
+int seed_alloc(const sas_index* x, uint64_t np, hipStream_t st, SeedState& s) {
     TRY(sas_scratch_pool(x, &s.pool));
     TRY(s.poff.alloc(s.pool, np * 8, st));
     TRY(s.plen.alloc(s.pool, np * 4, st));
     TRY(s.lohi.alloc(s.pool, np * 16, st));
     TRY(s.coff.alloc(s.pool, (np + 1) * 8, st));
+    s.lo = s.lohi.as<uint64_t>();
+    s.hi = s.lo + np;
+    return 0;
+}
+
+int seed_ranges(const sas_index* x, const uint8_t* qbytes, uint64_t np, hipStream_t st, uint32_t flags, SeedState& s) {
+    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
+    return sas_search_range(x, qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, s.lo, s.hi, st, rflags);
+}
+
+int seed_offsets(const sas_index* x, uint64_t np, hipStream_t st, SeedState& s) {
+    return sas_locate_offsets(x, s.lo, s.hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS);
+}
+
+int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t max_m,
+                    bool skip_mask, uint8_t* qflags, hipStream_t st, uint32_t flags, SeedState& s) {
+    const uint32_t kp1 = k + 1;
+    const uint64_t nq = Q.nq, np = nq * kp1;
+    TRY(seed_alloc(x, np, st, s));
     if (skip_mask) TRY(s.skip.alloc(s.pool, nq * 2, st));
     if (!qflags) {
         TRY(s.qfl.alloc(s.pool, nq, st));
         qflags = s.qfl.as<uint8_t>();
     }
-    s.lo = s.lohi.as<uint64_t>();
-    s.hi = s.lo + np;
     hipLaunchKernelGGL(k_mm_pieces, seed_grid(x, np), dim3(256), 0, st, Q, kp1, s.poff.as<uint64_t>(),
                        s.plen.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    const uint32_t rflags = (flags & (SAS_NO_PREFIX_TABLE | SAS_VALIDATE)) | SAS_DEVICE_PTRS;
-    TRY(sas_search_range(x, Q.qbytes, s.poff.as<uint64_t>(), s.plen.as<uint32_t>(), np, s.lo, s.hi, st, rflags));
+    TRY(seed_ranges(x, Q.qbytes, np, st, flags, s));
     hipLaunchKernelGGL(k_seed_gate, seed_grid(x, nq), dim3(256), 0, st, Q, kp1, max_seed_hits, max_m, s.lo, s.hi,
                        s.skip.as<uint16_t>(), qflags);
     HIP_TRY(hipGetLastError());
-    return sas_locate_offsets(x, s.lo, s.hi, np, 0, s.coff.as<uint64_t>(), st, SAS_DEVICE_PTRS);
+    return seed_offsets(x, np, st, s);
 }

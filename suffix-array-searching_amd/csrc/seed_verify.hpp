@@ -116,6 +116,15 @@ struct SeedState {
     uint64_t* hi = nullptr;
 };
 
+// The three stages of seed_candidates that do not depend on how a query is cut, for a call that
+// cuts it otherwise (sas_mems.hip: overlapping windows, one per query offset): the scratch of np
+// seeds (poff, plen, lohi, coff; lo and hi set), sas_search_range over the seeds that the caller
+// wrote into poff / plen (flags: the call's; SAS_NO_PREFIX_TABLE and SAS_VALIDATE are passed on),
+// and sas_locate_offsets on the ranges as the caller's gate left them.  No host read
+int seed_alloc(const sas_index* x, uint64_t np, hipStream_t st, SeedState& s);
+int seed_ranges(const sas_index* x, const uint8_t* qbytes, uint64_t np, hipStream_t st, uint32_t flags, SeedState& s);
+int seed_offsets(const sas_index* x, uint64_t np, hipStream_t st, SeedState& s);
+
 // All arrays on the device.  A query of more than max_m chars gets no seeds and SAS_ED_LONG;
 // skip_mask: s.skip gets, per query, a u16 whose bit j says that piece j is no seed; qflags (may
 // be null): the per-query flags, SAS_MM_* = SAS_ED_*.  No host read

@@ -31,6 +31,9 @@ SAS_LOCATE_NO_PARTITION = 1 << 30
 SAS_ROUTE_PACKED = 1 << 26
 SAS_MM_TRUNCATED = 1  # sas_locate_mismatch's per-query flags
 SAS_MM_SHORT = 2
+SAS_MEM_TRUNCATED = 1  # sas_mems' per-query flags
+SAS_MEM_SHORT = 2
+SAS_MEM_UNIQUE = 1 << 1  # its call flag: only matches whose string occurs once in the text
 SAS_ED_TRUNCATED = 1  # sas_locate_edit's per-query flags
 SAS_ED_SHORT = 2
 SAS_ED_LONG = 4
@@ -193,6 +196,10 @@ def lib():
     L.sas_locate_mismatch_fixed.argtypes = [vp, vp, u32, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
     L.sas_locate_mismatch_verify_ms.argtypes = [vp]
     L.sas_locate_mismatch_verify_ms.restype = C.c_double
+    L.sas_mems.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, u64, vp, vp, u32]
+    L.sas_mems_fixed.argtypes = [vp, vp, u32, u64, u32, u64, vp, vp, vp, vp, vp, u64, vp, vp, u32]
+    L.sas_mems_verify_ms.argtypes = [vp]
+    L.sas_mems_verify_ms.restype = C.c_double
     L.sas_locate_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
     L.sas_locate_edit_fixed.argtypes = [vp, vp, u32, u64, u32, u64, vp, vp, vp, vp, u64, vp, vp, u32]
     L.sas_locate_edit_verify_ms.argtypes = [vp]

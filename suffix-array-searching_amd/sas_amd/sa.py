@@ -634,6 +634,40 @@ class SaNaive:
         q = _queries(qbytes, None, None, m, stream, u32, "locate_mismatch")
         return self._locate_mismatch("sas_locate_mismatch", q, k, max_seed_hits, dist, out, capacity, flags)
 
+    # -- maximal exact matches (sas_mems*)
+    def _mems(self, q, min_len, max_hits, unique, out, capacity, flags):
+        side, nq, lead, suffix = q
+        f = getattr(lib(), "sas_mems" + suffix)
+        off, qfl = side.new("u64", nq + 1), side.new("u8", nq)
+        flags |= _lib.SAS_MEM_UNIQUE if unique else 0
+
+        def call(bufs, cap, total):
+            return f(self._h, *lead, int(min_len), int(max_hits), _ptr(off), _ptr(bufs[1]), _ptr(bufs[0]),
+                     _ptr(bufs[2]), _ptr(qfl), int(cap), total, side.stream, flags | side.flags)
+        (tpos, qpos, ln), _ = sized(side, "mems" + suffix, call, off, nq, ("pos", "u32", "u32"), out, capacity)
+        return off, qpos, tpos, ln, qfl
+
+    def mems(self, qbytes, qoff, qlen, min_len: int, max_hits: int = 0, unique: bool = False, u32: bool = False,
+             stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """Every maximal exact match of at least min_len chars between every ragged query
+        qbytes[qoff[k] : qoff[k] + qlen[k]] and the text (sas_mems): (off, qpos, tpos, len, qflags).
+        Query k's matches are the entries off[k] : off[k + 1]: query[qpos : qpos + len] ==
+        text[tpos : tpos + len], extendable neither to the left nor to the right, ordered by qpos,
+        then by the SA rank of tpos.  qflags[k] is a mask of SAS_MEM_TRUNCATED (a query offset whose
+        first min_len chars occur more than max_hits times was skipped; 0: no limit) and
+        SAS_MEM_SHORT (len < min_len: no result).  unique: only matches whose string occurs once in
+        the text.  numpy in -> numpy out (a sizing call, then the real one); torch CUDA in -> CUDA
+        out: with out (the tpos buffer) / capacity one call that writes nothing at or past the
+        capacity (the caller checks off[nq]), otherwise a sizing call first."""
+        return self._mems(_queries(qbytes, qoff, qlen, 0, stream, u32), min_len, max_hits, unique, out, capacity,
+                          flags)
+
+    def mems_fixed(self, qbytes, m: int, min_len: int, max_hits: int = 0, unique: bool = False, u32: bool = False,
+                   stream=None, out=None, capacity: int | None = None, flags: int = 0):
+        """mems for fixed-length queries qbytes[k*m : (k+1)*m] (sas_mems_fixed)."""
+        return self._mems(_queries(qbytes, None, None, m, stream, u32, "mems"), min_len, max_hits, unique, out,
+                          capacity, flags)
+
     def locate_edit(self, qbytes, qoff, qlen, k: int, max_seed_hits: int = 0, u32: bool = False,
                     dist: bool = True, stream=None, out=None, capacity: int | None = None, flags: int = 0):
         """Every end position of every ragged query qbytes[qoff[i] : qoff[i] + qlen[i]] within edit
