@@ -8,22 +8,21 @@ int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& wh
     return 0;
 }
 
-int HostQueries::stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                       const uint32_t* qlen, uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q) {
+int HostQueries::stage(const char* label, const QueryArgs& q, uint64_t nq, hipStream_t st, MmQueries* Q) {
     const std::string l(label);
-    uint64_t span = nq * (uint64_t)m;
-    if (ragged) {
+    uint64_t span = nq * (uint64_t)q.m;
+    if (q.ragged) {
         span = 0;
-        for (uint64_t i = 0; i < nq; i++) span = std::max(span, qoff[i] + qlen[i]);
+        for (uint64_t i = 0; i < nq; i++) span = std::max(span, q.qoff[i] + q.qlen[i]);
     }
     TRY(dq.alloc(span + 64, (l + " queries").c_str()));  // the packers read whole words past the end
     HIP_TRY(hipStreamSynchronize(st));
-    if (span) HIP_TRY(hipMemcpy(dq.p, qbytes, span, hipMemcpyHostToDevice));
-    if (ragged) {
-        TRY(host_copy_in(dqoff, qoff, nq * 8, l + " query offsets"));
-        TRY(host_copy_in(dqlen, qlen, nq * 4, l + " query lengths"));
+    if (span) HIP_TRY(hipMemcpy(dq.p, q.qbytes, span, hipMemcpyHostToDevice));
+    if (q.ragged) {
+        TRY(host_copy_in(dqoff, q.qoff, nq * 8, l + " query offsets"));
+        TRY(host_copy_in(dqlen, q.qlen, nq * 4, l + " query lengths"));
     }
-    *Q = MmQueries{dq.as<uint8_t>(), ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), m, nq};
+    *Q = MmQueries{dq.as<uint8_t>(), q.ragged ? dqoff.as<uint64_t>() : nullptr, dqlen.as<uint32_t>(), q.m, nq};
     return 0;
 }
 
@@ -42,6 +41,18 @@ int HostOutputs::copy_back(hipStream_t st) {
     for (; copied < count; copied++)
         if (bytes[copied])
             HIP_TRY(hipMemcpyAsync(host[copied], dev[copied].p, bytes[copied], hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+int host_list_total(HostOutputs& ho, hipStream_t st, const std::string& fn, const char* noun, const char* hint,
+                    const uint64_t* out_off, uint64_t nq, uint64_t capacity, uint64_t* out_total, uint64_t* total) {
+    TRY(ho.copy_back(st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *total = out_off[nq];
+    if (out_total) *out_total = *total;
+    if (*total > capacity)
+        SAS_FAIL(ENOSPC, fn + ": " + std::to_string(*total) + " " + noun + ", capacity " + std::to_string(capacity) +
+                             " (size " + hint + " from *out_total and call again)");
     return 0;
 }
 

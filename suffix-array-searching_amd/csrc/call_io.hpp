@@ -3,9 +3,12 @@
 //
 //   * PoolBuf, pool_scan: stream-ordered scratch from a memory pool (the index's:
 //     sas_scratch_pool) and rocPRIM's exclusive scan with its temp buffer from that pool;
+//   * QueryArgs: the query argument of a call, ragged or fixed-length, as one value;
 //   * host_copy_in, HostQueries, HostOutputs: the host-pointer path of a call, host arrays in,
 //     device twins, copy back.  It is synchronous on purpose, plain hipMalloc (DevBuf) and
 //     hipMemcpy: the stream-ordered allocator + pageable async copies raced on the null stream;
+//   * host_list_total: the step between the two passes of a call that returns per-query lists
+//     on host pointers (offsets back, the total reported, ENOSPC);
 //   * BadFlag: the per-call invalid-input flag word.
 #pragma once
 #include "build_util.hpp"
@@ -50,6 +53,20 @@ struct MmQueries {
     __device__ __forceinline__ uint32_t len(uint64_t q) const { return qoff ? qlen[q] : m; }
 };
 
+// The query argument as a call's extern "C" wrapper got it: ragged (qoff, qlen) or nq queries of
+// m chars each.  The pointers are the caller's, of either kind
+struct QueryArgs {
+    const uint8_t* qbytes;
+    const uint64_t* qoff;
+    const uint32_t* qlen;
+    uint32_t m;
+    bool ragged;
+    // no pointer that nq queries need is null
+    bool null_ok(uint64_t nq) const { return !nq || (qbytes && (!ragged || (qoff && qlen))); }
+    // device pointers: the batch as the kernels see it
+    MmQueries device(uint64_t nq) const { return MmQueries{qbytes, ragged ? qoff : nullptr, qlen, m, nq}; }
+};
+
 // src[0 .. bytes) of the host in a device buffer of its own (synchronous)
 int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& what);
 
@@ -58,8 +75,7 @@ int host_copy_in(DevBuf& d, const void* src, size_t bytes, const std::string& wh
 struct HostQueries {
     DevBuf dq, dqoff, dqlen;
     // Waits for `st`, then copies (synchronous).  label: the call's word in "<label> queries"
-    int stage(const char* label, const uint8_t* qbytes, bool ragged, const uint64_t* qoff, const uint32_t* qlen,
-              uint32_t m, uint64_t nq, hipStream_t st, MmQueries* Q);
+    int stage(const char* label, const QueryArgs& q, uint64_t nq, hipStream_t st, MmQueries* Q);
 };
 
 // The host-pointer path's way out: the device twins of a call's host outputs.  twin() allocates
@@ -81,6 +97,14 @@ struct HostOutputs {
     }
     int copy_back(hipStream_t st);
 };
+
+// Between the two passes of a host-pointer call that returns per-query lists (sas_locate, and
+// seed_list_call's: seed_verify.hpp): copies the twins made so far back, the offsets among them,
+// and waits; the total out_off[nq] goes to *total and, where the caller asked, *out_total.  A
+// total above the capacity is ENOSPC, "<fn>: <total> <noun>, capacity <capacity> (size <hint>
+// from *out_total and call again)", with the offsets and the total written
+int host_list_total(HostOutputs& ho, hipStream_t st, const std::string& fn, const char* noun, const char* hint,
+                    const uint64_t* out_off, uint64_t nq, uint64_t capacity, uint64_t* out_total, uint64_t* total);
 
 // The invalid-input flag of one call: a 4-byte word of the call's own (plain hipMalloc, not the
 // pool) that its kernels OR into, so that concurrent calls on other streams (allowed: the index

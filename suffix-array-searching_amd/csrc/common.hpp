@@ -308,6 +308,14 @@ void with_sa_w(uint32_t sa_w, F&& f) {
     else f(std::integral_constant<int, 4>{});
 }
 
+// A bool of the call (SAS_LOCATE_U32, an index with a layout, ...) as a compile-time constant,
+// f(std::bool_constant<B>): one launch serves both instantiations of a kernel
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // Writes: byte stores, so neighbouring entries written by other lanes never race.
 template <int W>
 __device__ __forceinline__ void sa_put(uint8_t* p, uint64_t i, uint64_t v) {

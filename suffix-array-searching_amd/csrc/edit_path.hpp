@@ -1,5 +1,6 @@
 // edit_path.hpp -- the seed / verify / sort path of sas_edit.hip for the calls built on it
-// (sas_edit.hip: sas_locate_edit itself; sas_map.hip: sas_map_edit over both strands).
+// (sas_edit.hip: sas_locate_edit itself; sas_map.hip: sas_map_edit over both strands), Myers'
+// bit-vector state and the dispatch on its word count (with_ed_words; sas_rescue.hip's too).
 #pragma once
 #include "seed_verify.hpp"
 
@@ -98,6 +99,17 @@ static inline uint32_t ed_bits(uint64_t v) {
     uint32_t b = 1;
     while (b < 64 && (v >> b)) b++;
     return b;
+}
+
+// The number of 64-row words of Myers' state that serves a batch, as a compile-time constant,
+// f(std::integral_constant<int, NW>): 1, 2 or 4 for fixed-length queries of m <= 64, 128, more
+// chars (a longer m is gated: any kernel serves), 0 for a ragged batch (by each query's m)
+template <class F>
+void with_ed_words(const MmQueries& Q, F&& f) {
+    if (Q.qoff) f(std::integral_constant<int, 0>{});
+    else if (Q.m <= 64) f(std::integral_constant<int, 1>{});
+    else if (Q.m <= 128) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
 }
 
 // All arrays on the device (out_qflags and out_total may be null).  Writes out_off[0 .. nq] and

@@ -35,7 +35,7 @@
 //                     read back from its locus) or the two single-read winners, every per-read
 //                     and per-pair record, and the request of one alignment per read.  Its RESCUE
 //                     instantiation (sas_map_pairs_rescue) puts the rescue winner between the two;
-//   5. sas_align_edit over those 2 np alignments, chained on the stream.
+//   5. sas_align_edit over those 2 np alignments, chained on the stream (align_winners).
 #pragma once
 #include "map_path.hpp"
 
@@ -45,16 +45,8 @@
 #define PR_EX_SHIFT 16
 #define PR_EX_MASK ((1ull << 41) - 1ull)
 
-struct PairOut {
-    void* end;
-    void* start;
-    uint8_t* dist;
-    uint8_t* strand;
-    uint32_t* nbest;
-    uint32_t* nloci;
-    uint8_t* nruns;
-    uint16_t* runs;
-    uint8_t* qflags;
+// The per-read outputs of 2 np reads (map_path.hpp) and the per-pair ones
+struct PairOut : ReadOut {
     uint8_t* pflags;
     uint32_t* npairs;
     uint32_t* nbestpairs;
@@ -91,6 +83,5 @@ typedef int (*PairDevice)(const sas_index* x, const MmQueries& Q, const PairCall
                           uint32_t flags);
 
 // The argument checks and the host-pointer path of a paired-end call around its device path
-int pairs_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-               const uint32_t* qlen, uint32_t m, uint64_t np, const PairCall& c, PairDevice device, const PairOut& o,
-               void* stream, uint32_t flags);
+int pairs_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t np, const PairCall& c, PairDevice device,
+               const PairOut& o, void* stream, uint32_t flags);

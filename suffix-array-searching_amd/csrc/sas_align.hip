@@ -259,15 +259,17 @@ __global__ void k_al_validate(const uint8_t* __restrict__ qb, const uint64_t* __
     if (b & 0xFCu) atomicOr(bad, 1u);
 }
 
-template <int KB>
-static void al_launch(dim3 grid, hipStream_t st, const AlArgs& a, bool u32) {
-    if (a.lay.nseq) {  // a kernel of its own: without a layout the parent's instructions run
-        if (u32) hipLaunchKernelGGL((k_al_align<KB, true, true>), grid, dim3(AL_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_al_align<KB, false, true>), grid, dim3(AL_BLOCK), 0, st, a);
-        return;
-    }
-    if (u32) hipLaunchKernelGGL((k_al_align<KB, true, false>), grid, dim3(AL_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_al_align<KB, false, false>), grid, dim3(AL_BLOCK), 0, st, a);
+// kb: the band's k rounded up to 1, 3, 7 or 15.  A kernel of its own for an index with a layout:
+// without one the parent's instructions run
+static void al_launch(uint32_t kb, bool u32, dim3 grid, hipStream_t st, const AlArgs& a) {
+    const auto launch = [&](auto KB) { with_bool(u32, [&](auto U32) { with_bool(a.lay.nseq != 0, [&](auto LAY) {
+        hipLaunchKernelGGL((k_al_align<decltype(KB)::value, decltype(U32)::value, decltype(LAY)::value>), grid,
+                           dim3(AL_BLOCK), 0, st, a);
+    }); }); };
+    if (kb == 1) launch(std::integral_constant<int, 1>{});
+    else if (kb == 3) launch(std::integral_constant<int, 3>{});
+    else if (kb == 7) launch(std::integral_constant<int, 7>{});
+    else launch(std::integral_constant<int, 15>{});
 }
 
 // All arrays on the device.  No host read unless `validate`
@@ -308,12 +310,7 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
     a.out_runs = out_runs;
     a.scr = scr.p;
     a.lay = x->lay;
-    const dim3 grid((unsigned)blocks);
-    const bool u32 = (flags & SAS_LOCATE_U32) != 0;
-    if (kb == 1) al_launch<1>(grid, st, a, u32);
-    else if (kb == 3) al_launch<3>(grid, st, a, u32);
-    else if (kb == 7) al_launch<7>(grid, st, a, u32);
-    else al_launch<15>(grid, st, a, u32);
+    al_launch(kb, (flags & SAS_LOCATE_U32) != 0, dim3((unsigned)blocks), st, a);
     HIP_TRY(hipGetLastError());
     if (validate) {
         uint32_t hbad = 0;
@@ -323,10 +320,9 @@ static int al_device(const char* fn, const sas_index* x, const MmQueries& Q, uin
     return 0;
 }
 
-static int align_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                      const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, const uint64_t* off, const void* end,
-                      uint64_t na, void* out_start, uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs,
-                      void* stream, uint32_t flags) {
+static int align_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint32_t k,
+                      const uint64_t* off, const void* end, uint64_t na, void* out_start, uint8_t* out_dist,
+                      uint8_t* out_nruns, uint16_t* out_runs, void* stream, uint32_t flags) {
     const std::string w(fn);
     if (!x) SAS_FAIL(EINVAL, w + ": null index");
     if (k > MM_MAX_K) SAS_FAIL(EINVAL, w + ": k must be 0.." + std::to_string(MM_MAX_K));
@@ -334,15 +330,13 @@ static int align_impl(const char* fn, const sas_index* x, const uint8_t* qbytes,
         SAS_FAIL(EINVAL, w + ": SAS_LOCATE_U32 needs a text of n < 2^32 chars");
     if (!x->text_w) SAS_FAIL(ENOTSUP, w + ": the index holds no packed text");
     if (na == 0) return 0;
-    if (!off || !end || !out_start || (nq && (!qbytes || (ragged && (!qoff || !qlen)))))
-        SAS_FAIL(EINVAL, w + ": null argument");
+    if (!off || !end || !out_start || !q.null_ok(nq)) SAS_FAIL(EINVAL, w + ": null argument");
     if (nq == 0) return 0;  // off[0] = 0: no alignment
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t stride = 2 * k + 1;
     if (flags & SAS_DEVICE_PTRS) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        return al_device(fn, x, Q, k, off, end, na, out_start, out_dist, out_nruns, out_runs, st, flags,
+        return al_device(fn, x, q.device(nq), k, off, end, na, out_start, out_dist, out_nruns, out_runs, st, flags,
                          (flags & SAS_VALIDATE) != 0);
     }
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
@@ -353,7 +347,7 @@ static int align_impl(const char* fn, const sas_index* x, const uint8_t* qbytes,
     HostOutputs ho;
     DevBuf doff, dend;
     MmQueries Q;
-    TRY(hq.stage("align", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
+    TRY(hq.stage("align", q, nq, st, &Q));
     TRY(host_copy_in(doff, off, (nq + 1) * 8, "align offsets"));
     TRY(host_copy_in(dend, end, count * esz, "align ends"));
     void* dstart;
@@ -373,14 +367,14 @@ extern "C" int sas_align_edit(const sas_index* x, const uint8_t* qbytes, const u
                               uint64_t nq, uint32_t k, const uint64_t* off, const void* end, uint64_t na,
                               void* out_start, uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs, void* stream,
                               uint32_t flags) {
-    return align_impl("sas_align_edit", x, qbytes, true, qoff, qlen, 0, nq, k, off, end, na, out_start, out_dist,
-                      out_nruns, out_runs, stream, flags);
+    return align_impl("sas_align_edit", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, k, off, end, na, out_start,
+                      out_dist, out_nruns, out_runs, stream, flags);
 }
 
 extern "C" int sas_align_edit_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
                                     const uint64_t* off, const void* end, uint64_t na, void* out_start,
                                     uint8_t* out_dist, uint8_t* out_nruns, uint16_t* out_runs, void* stream,
                                     uint32_t flags) {
-    return align_impl("sas_align_edit_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, off, end, na, out_start,
-                      out_dist, out_nruns, out_runs, stream, flags);
+    return align_impl("sas_align_edit_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, k, off, end, na,
+                      out_start, out_dist, out_nruns, out_runs, stream, flags);
 }

@@ -236,34 +236,20 @@ __global__ void k_ed_scatter(const uint64_t* __restrict__ keys, const uint8_t* _
 }
 
 // SAS_ED_TIMING=1: the verify kernel and the de-duplication (k_ed_emit .. k_ed_offsets) of every
-// call are timed with HIP events (synchronises); sas_locate_edit_verify_ms and
-// sas_locate_edit_dedup_ms return the calling thread's last figures
-static thread_local double ed_last_verify_ms = -1.0;
-static thread_local double ed_last_dedup_ms = -1.0;  // k_ed_emit .. k_ed_offsets
-static thread_local uint64_t ed_last_candidates = 0, ed_last_proposals = 0;
-static bool ed_timing() {
-    const char* e = getenv("SAS_ED_TIMING");
-    return e && e[0] == '1';
-}
+// call are timed; sas_locate_edit_verify_ms and sas_locate_edit_dedup_ms return the calling
+// thread's last figures
+static thread_local SeedTiming ed_timing{"SAS_ED_TIMING"};
 
-extern "C" double sas_locate_edit_verify_ms(uint64_t* candidates) {
-    if (candidates) *candidates = ed_last_candidates;
-    return ed_last_verify_ms;
-}
+extern "C" double sas_locate_edit_verify_ms(uint64_t* candidates) { return ed_timing.get(0, candidates); }
 
-extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) {
-    if (proposals) *proposals = ed_last_proposals;
-    return ed_last_dedup_ms;
-}
+extern "C" double sas_locate_edit_dedup_ms(uint64_t* proposals) { return ed_timing.get(1, proposals); }
 
 // a kernel of its own for an index with a layout: without one the parent's instructions run
-template <int NW>
 static void ed_launch_verify(const sas_index* x, dim3 grid, hipStream_t st, const EdArgs& a) {
-    with_sa_w(x->sa_w, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        if (x->lay.nseq) hipLaunchKernelGGL((k_ed_verify<W, NW, true>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_ed_verify<W, NW, false>), grid, dim3(MM_BLOCK), 0, st, a);
-    });
+    with_sa_w(x->sa_w, [&](auto W) { with_ed_words(a.Q, [&](auto NW) { with_bool(x->lay.nseq != 0, [&](auto LAY) {
+        hipLaunchKernelGGL((k_ed_verify<decltype(W)::value, decltype(NW)::value, decltype(LAY)::value>), grid,
+                           dim3(MM_BLOCK), 0, st, a);
+    }); }); });
 }
 
 // All arrays on the device (out_total may be null).  Two host reads: the candidate total and
@@ -273,22 +259,14 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     const uint32_t kp1 = k + 1;
     const uint64_t nq = Q.nq, np = nq * kp1;
     s.ebits = ed_bits(x->n);
-    const auto nothing = [&]() {
-        HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
-        if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-        return 0;
-    };
     // 1 to 4: a query of more than SAS_ED_MAX_M chars gets no seeds
     TRY(seed_candidates(x, Q, k, max_seed_hits, SAS_ED_MAX_M, false, out_qflags, st, flags, s.seed));
     hipMemPool_t pool = s.seed.pool;
     uint64_t* coff = s.seed.coff.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(&s.C, coff + np, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(seed_read_total(coff + np, st, &s.C));
     const uint64_t C = s.C;
-    ed_last_candidates = C;
-    ed_last_verify_ms = ed_last_dedup_ms = -1.0;
-    ed_last_proposals = 0;
-    if (C == 0) return nothing();
+    ed_timing.reset(C);
+    if (C == 0) return seed_nothing(out_off, nq, out_total, st);
     TRY(s.mask.alloc(pool, (C + 1) * 4, st));
     TRY(s.kbase.alloc(pool, C * 8, st));
     TRY(s.dists.alloc(pool, C * 16, st));
@@ -309,26 +287,18 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     a.kbase = s.kbase.as<uint64_t>();
     a.dists = s.dists.as<ulonglong2>();
     a.lay = x->lay;
-    uint64_t blocks = (C + MM_T - 1) / MM_T;
-    if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
-    const dim3 vgrid((unsigned)tile_grid(blocks));
-    SeedTimer timer(ed_timing(), st);
+    SeedTimer timer(ed_timing.on(), st);
     TRY(timer.start());
-    // fixed-length batches: the word count from m (a longer m is gated: any kernel serves)
-    if (Q.qoff) ed_launch_verify<0>(x, vgrid, st, a);
-    else if (Q.m <= 64) ed_launch_verify<1>(x, vgrid, st, a);
-    else if (Q.m <= 128) ed_launch_verify<2>(x, vgrid, st, a);
-    else ed_launch_verify<4>(x, vgrid, st, a);
+    ed_launch_verify(x, seed_verify_grid(C), st, a);
     HIP_TRY(hipGetLastError());
-    TRY(timer.stop(&ed_last_verify_ms));
+    TRY(timer.stop(&ed_timing.ms[0]));
     // proposals: one per accepted end of every candidate
     TRY(pool_scan(pool, st, rocprim::make_transform_iterator(s.mask.as<uint32_t>(), EdPopcount{}),
                 s.pscan.as<uint64_t>(), C + 1));
-    HIP_TRY(hipMemcpyAsync(&s.P, s.pscan.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(seed_read_total(s.pscan.as<uint64_t>() + C, st, &s.P));
     const uint64_t P = s.P;
-    ed_last_proposals = P;
-    if (P == 0) return nothing();
+    ed_timing.count[1] = P;
+    if (P == 0) return seed_nothing(out_off, nq, out_total, st);
     TRY(timer.start());
     TRY(s.keys.alloc(pool, 2 * P * 8, st));
     TRY(s.vals.alloc(pool, 2 * P, st));
@@ -356,88 +326,52 @@ int ed_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_
     hipLaunchKernelGGL(k_ed_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, s.skeys, s.uscan.as<uint64_t>(), P, nq,
                        s.ebits, out_off, out_total);
     HIP_TRY(hipGetLastError());
-    return timer.stop(&ed_last_dedup_ms);
+    return timer.stop(&ed_timing.ms[1]);
 }
 
 static int ed_scatter(const sas_index* x, EdState& s, void* out_end, uint8_t* out_dist, uint64_t capacity,
                       hipStream_t st, uint32_t flags) {
     if (s.P == 0 || capacity == 0) return 0;
     const dim3 grid(std::min(grid_for(s.P), (unsigned)x->num_cus * 8));
-    if (flags & SAS_LOCATE_U32)
-        hipLaunchKernelGGL(k_ed_scatter<true>, grid, dim3(256), 0, st, s.skeys, s.svals, s.uscan.as<uint64_t>(), s.P,
-                           s.ebits, out_end, out_dist, capacity);
-    else
-        hipLaunchKernelGGL(k_ed_scatter<false>, grid, dim3(256), 0, st, s.skeys, s.svals, s.uscan.as<uint64_t>(), s.P,
-                           s.ebits, out_end, out_dist, capacity);
+    with_bool(flags & SAS_LOCATE_U32, [&](auto U32) {
+        hipLaunchKernelGGL(k_ed_scatter<decltype(U32)::value>, grid, dim3(256), 0, st, s.skeys, s.svals,
+                           s.uscan.as<uint64_t>(), s.P, s.ebits, out_end, out_dist, capacity);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-static int edit_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                     const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
-                     uint64_t* out_off, void* out_end, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
-                     uint64_t* out_total, void* stream, uint32_t flags) {
+static int edit_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint32_t k,
+                     uint64_t max_seed_hits, uint64_t* out_off, void* out_end, uint8_t* out_dist, uint8_t* out_qflags,
+                     uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
     const std::string w(fn);
     TRY(seed_index_checks(w, x, k, flags, stream));
-    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
-    if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_end) ||
-        (!dev && !out_total))
-        SAS_FAIL(EINVAL, w + ": null argument");
-    // the (query, end) sort key: the bits of an end in [0, n] above those of a query number
-    if (ed_bits(x->n) + (nq > 1 ? ed_bits(nq - 1) : 0) > 64)
-        SAS_FAIL(EINVAL, w + ": " + std::to_string(nq) + " queries on a text of " + std::to_string(x->n) +
-                             " chars do not fit the 64-bit (query, end) sort key: split the batch");
-    HIP_TRY(hipSetDevice(x->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (nq == 0) {
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(out_off, 0, 8, st));
-            if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-        } else {
-            out_off[0] = 0;
-            *out_total = 0;
-        }
-        return 0;
-    }
     EdState s;
-    if (dev) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        TRY(ed_prepare(x, Q, k, max_seed_hits, out_off, out_qflags, out_total, st, flags, s));
-        return ed_scatter(x, s, out_end, out_dist, capacity, st, flags);
-    }
-    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    HostQueries hq;
-    HostOutputs ho;
-    MmQueries Q;
-    TRY(hq.stage("edit", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
-    uint64_t* doff;
-    uint8_t* dfl;
-    TRY(ho.twin(out_off, (nq + 1) * 8, "edit result offsets", &doff));
-    TRY(ho.twin(out_qflags, nq, "edit query flags", &dfl));
-    TRY(ed_prepare(x, Q, k, max_seed_hits, doff, dfl, nullptr, st, flags | SAS_VALIDATE, s));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t total = out_off[nq];
-    *out_total = total;
-    if (total > capacity)
-        SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " ends, capacity " + std::to_string(capacity) +
-                             " (size out_end from *out_total and call again)");
-    if (total == 0) return 0;
-    void* dend;
-    uint8_t* ddist;
-    TRY(ho.twin(out_end, total * ((flags & SAS_LOCATE_U32) ? 4 : 8), "edit ends", &dend));
-    TRY(ho.twin(out_dist, total, "edit distances", &ddist));
-    TRY(ed_scatter(x, s, dend, ddist, total, st, flags));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    const ListOut outs[] = {{out_end, (flags & SAS_LOCATE_U32) ? 4u : 8u, "edit ends", true},
+                            {out_dist, 1, "edit distances", false}};
+    // the (query, end) sort key: the bits of an end in [0, n] above those of a query number
+    const auto key_fits = [&]() {
+        if (ed_bits(x->n) + (nq > 1 ? ed_bits(nq - 1) : 0) > 64)
+            SAS_FAIL(EINVAL, w + ": " + std::to_string(nq) + " queries on a text of " + std::to_string(x->n) +
+                                 " chars do not fit the 64-bit (query, end) sort key: split the batch");
+        return 0;
+    };
+    return seed_list_call(
+        {fn, "edit", "ends", "out_end", key_fits}, x, q, nq, out_off, out_qflags, outs, 2, capacity, out_total, stream,
+        flags,
+        [&](const MmQueries& Q, uint64_t* off, uint8_t* qfl, uint64_t* total, hipStream_t st, uint32_t fl) {
+            return ed_prepare(x, Q, k, max_seed_hits, off, qfl, total, st, fl, s);
+        },
+        [&](void* const* out, uint64_t cap, hipStream_t st) {
+            return ed_scatter(x, s, out[0], static_cast<uint8_t*>(out[1]), cap, st, flags);
+        });
 }
 
 extern "C" int sas_locate_edit(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
                                uint64_t nq, uint32_t k, uint64_t max_seed_hits, uint64_t* out_off, void* out_end,
                                uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
                                void* stream, uint32_t flags) {
-    return edit_impl("sas_locate_edit", x, qbytes, true, qoff, qlen, 0, nq, k, max_seed_hits, out_off, out_end,
+    return edit_impl("sas_locate_edit", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, k, max_seed_hits, out_off, out_end,
                      out_dist, out_qflags, capacity, out_total, stream, flags);
 }
 
@@ -445,6 +379,6 @@ extern "C" int sas_locate_edit_fixed(const sas_index* x, const uint8_t* qbytes, 
                                      uint64_t max_seed_hits, uint64_t* out_off, void* out_end, uint8_t* out_dist,
                                      uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
                                      uint32_t flags) {
-    return edit_impl("sas_locate_edit_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, max_seed_hits, out_off,
-                     out_end, out_dist, out_qflags, capacity, out_total, stream, flags);
+    return edit_impl("sas_locate_edit_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, k, max_seed_hits,
+                     out_off, out_end, out_dist, out_qflags, capacity, out_total, stream, flags);
 }

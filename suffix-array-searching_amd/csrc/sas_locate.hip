@@ -249,12 +249,10 @@ template <class SA>
 static void launch_fill(bool u32, dim3 grid, hipStream_t st, SA sa, const sas_index* x, const uint64_t* lo,
                         const uint64_t* off, uint64_t nq, void* out, uint64_t capacity, const LocTile* tile_q,
                         uint64_t ntiles) {
-    if (u32)
-        hipLaunchKernelGGL((k_locate_fill<SA, true>), grid, dim3(LOC_BLOCK), 0, st, sa, x->sa_n, x->rank_lo, lo, off, nq,
-                           out, capacity, tile_q, ntiles);
-    else
-        hipLaunchKernelGGL((k_locate_fill<SA, false>), grid, dim3(LOC_BLOCK), 0, st, sa, x->sa_n, x->rank_lo, lo, off,
-                           nq, out, capacity, tile_q, ntiles);
+    with_bool(u32, [&](auto U32) {
+        hipLaunchKernelGGL((k_locate_fill<SA, decltype(U32)::value>), grid, dim3(LOC_BLOCK), 0, st, sa, x->sa_n,
+                           x->rank_lo, lo, off, nq, out, capacity, tile_q, ntiles);
+    });
 }
 
 extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uint64_t* out_off, uint64_t nq,
@@ -300,12 +298,17 @@ extern "C" int sas_locate_fill(const sas_index* x, const uint64_t* lo, const uin
     return 0;
 }
 
-// range search, offsets, fill; ragged (qoff, qlen) or fixed-length (qoff == nullptr)
-static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, uint32_t m_fixed, bool ragged,
-                       const uint64_t* qoff, const uint32_t* qlen, uint64_t nq, uint64_t max_per_query,
+static int locate_ranges(const sas_index* x, const QueryArgs& q, uint64_t nq, uint64_t* lo, uint64_t* hi, void* stream,
+                         uint32_t flags) {
+    return q.ragged ? sas_search_range(x, q.qbytes, q.qoff, q.qlen, nq, lo, hi, stream, flags)
+                    : sas_search_range_fixed(x, q.qbytes, q.m, nq, lo, hi, stream, flags);
+}
+
+// range search, offsets, fill; ragged (qoff, qlen) or fixed-length
+static int locate_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint64_t max_per_query,
                        uint64_t* out_off, void* out_pos, uint64_t capacity, uint64_t* out_total, void* stream,
                        uint32_t flags) {
-    if (!x || !out_off || (nq && !qbytes) || (capacity && !out_pos))
+    if (!x || !out_off || (nq && !q.qbytes) || (capacity && !out_pos))
         SAS_FAIL(EINVAL, std::string(fn) + ": null argument");
     TRY(locate_checks(fn, x, flags));
     const uint32_t sflags = flags & ~(uint32_t)(SAS_LOCATE_U32 | SAS_LOCATE_NO_PARTITION);
@@ -320,8 +323,7 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
         TRY(lohi.alloc(pool, nq * 16, st));
         uint64_t* lo = lohi.as<uint64_t>();
         uint64_t* hi = lo + nq;
-        int rc = ragged ? sas_search_range(x, qbytes, qoff, qlen, nq, lo, hi, stream, sflags)
-                        : sas_search_range_fixed(x, qbytes, m_fixed, nq, lo, hi, stream, sflags);
+        int rc = locate_ranges(x, q, nq, lo, hi, stream, sflags);
         if (!rc) rc = sas_locate_offsets(x, lo, hi, nq, max_per_query, out_off, stream, lflags);
         if (!rc) rc = sas_locate_fill(x, lo, out_off, nq, out_pos, capacity, stream, lflags);
         if (!rc && out_total && hipMemcpyAsync(out_total, out_off + nq, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
@@ -332,8 +334,7 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
     }
     // host arrays: ranges through the staged host pipeline, then one device result buffer
     std::vector<uint64_t> hr(nq ? 2 * nq : 1);  // lo, then hi: one buffer and one copy
-    if (ragged) TRY(sas_search_range(x, qbytes, qoff, qlen, nq, hr.data(), hr.data() + nq, stream, sflags));
-    else TRY(sas_search_range_fixed(x, qbytes, m_fixed, nq, hr.data(), hr.data() + nq, stream, sflags));
+    TRY(locate_ranges(x, q, nq, hr.data(), hr.data() + nq, stream, sflags));
     DevBuf dr;
     HostOutputs ho;
     TRY(host_copy_in(dr, hr.data(), nq * 16, "locate ranges"));
@@ -341,13 +342,8 @@ static int locate_impl(const char* fn, const sas_index* x, const uint8_t* qbytes
     uint64_t* doff;
     TRY(ho.twin(out_off, (nq + 1) * 8, "locate offsets", &doff));
     TRY(sas_locate_offsets(x, lo, lo + nq, nq, max_per_query, doff, stream, lflags));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t total = out_off[nq];
-    if (out_total) *out_total = total;
-    if (total > capacity)
-        SAS_FAIL(ENOSPC, std::string(fn) + ": " + std::to_string(total) + " positions, capacity " +
-                             std::to_string(capacity) + " (size out_pos from *out_total and call again)");
+    uint64_t total;
+    TRY(host_list_total(ho, st, fn, "positions", "out_pos", out_off, nq, capacity, out_total, &total));
     if (total == 0) return 0;
     void* dpos;
     TRY(ho.twin(out_pos, total * esz, "locate positions", &dpos));
@@ -361,13 +357,13 @@ extern "C" int sas_locate(const sas_index* x, const uint8_t* qbytes, const uint6
                           uint64_t nq, uint64_t max_per_query, uint64_t* out_off, void* out_pos, uint64_t capacity,
                           uint64_t* out_total, void* stream, uint32_t flags) {
     if (nq && (!qoff || !qlen)) SAS_FAIL(EINVAL, "sas_locate: null qoff/qlen");
-    return locate_impl("sas_locate", x, qbytes, 0, true, qoff, qlen, nq, max_per_query, out_off, out_pos, capacity,
-                       out_total, stream, flags);
+    return locate_impl("sas_locate", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, max_per_query, out_off, out_pos,
+                       capacity, out_total, stream, flags);
 }
 
 extern "C" int sas_locate_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq,
                                 uint64_t max_per_query, uint64_t* out_off, void* out_pos, uint64_t capacity,
                                 uint64_t* out_total, void* stream, uint32_t flags) {
-    return locate_impl("sas_locate_fixed", x, qbytes, m, false, nullptr, nullptr, nq, max_per_query, out_off, out_pos,
-                       capacity, out_total, stream, flags);
+    return locate_impl("sas_locate_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, max_per_query, out_off,
+                       out_pos, capacity, out_total, stream, flags);
 }

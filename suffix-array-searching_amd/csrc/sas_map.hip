@@ -351,36 +351,33 @@ __global__ void k_map_finalize(MapFin a) {
     }
 }
 
-struct MapOut {
-    void* end;
-    void* start;
-    uint8_t* dist;
-    uint8_t* strand;
-    uint32_t* nbest;
-    uint32_t* nloci;
-    uint8_t* nruns;
-    uint16_t* runs;
-    uint8_t* qflags;
-};
+int twin_reads(HostOutputs& ho, const ReadOut& host, uint64_t nq, uint64_t esz, uint64_t stride, const char* label,
+               ReadOut* dev) {
+    const std::string l(label);
+    TRY(ho.twin(host.end, nq * esz, (l + " ends").c_str(), &dev->end));
+    TRY(ho.twin(host.dist, nq, (l + " distances").c_str(), &dev->dist));
+    TRY(ho.twin(host.start, nq * esz, (l + " starts").c_str(), &dev->start));
+    TRY(ho.twin(host.strand, nq, (l + " strands").c_str(), &dev->strand));
+    TRY(ho.twin(host.nbest, nq * 4, (l + " best counts").c_str(), &dev->nbest));
+    TRY(ho.twin(host.nloci, nq * 4, (l + " locus counts").c_str(), &dev->nloci));
+    TRY(ho.twin(host.nruns, nq, (l + " run counts").c_str(), &dev->nruns));
+    TRY(ho.twin(host.runs, nq * stride * 2, (l + " runs").c_str(), &dev->runs));
+    TRY(ho.twin(host.qflags, nq, (l + " query flags").c_str(), &dev->qflags));
+    return 0;
+}
 
 // All arrays on the device; Q: the caller's queries
 static int map_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t max_seed_hits, uint32_t strands,
-                      const MapOut& o, hipStream_t st, uint32_t flags) {
+                      const ReadOut& o, hipStream_t st, uint32_t flags) {
     const uint64_t nq = Q.nq;
-    hipMemPool_t pool;
-    TRY(sas_scratch_pool(x, &pool));
     // 1..3. the batch, its sorted proposals, the slots
     MapState ms;
     TRY(map_select_batch(x, Q, k, max_seed_hits, strands, st, flags, ms));
-    const MmQueries& B = ms.B;
     // 4. the records and the alignment request
-    PoolBuf areq;
-    const bool align = o.start || o.nruns || o.runs;
-    const bool u32 = (flags & SAS_LOCATE_U32) != 0;
-    const uint64_t esz = u32 ? 4 : 8;
-    TRY(areq.alloc(pool, (nq + 1) * 8 + nq * 8 + nq * 4 + (o.start ? 0 : nq * esz), st));
+    AlignReq areq;
+    TRY(areq.alloc(x, nq, o.start, flags, st));
     MapFin f{};
-    f.B = B;
+    f.B = ms.B;
     f.nq = nq;
     f.n = x->n;
     f.strands = strands;
@@ -394,22 +391,19 @@ static int map_device(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     f.out_nbest = o.nbest;
     f.out_nloci = o.nloci;
     f.out_qflags = o.qflags;
-    f.aoff = areq.as<uint64_t>();
-    f.aqoff = f.aoff + nq + 1;
-    void* scratch_start = f.aqoff + nq;                  // 8-byte aligned; unused when out_start is given
-    f.aqlen = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch_start) + (o.start ? 0 : nq * esz));
-    if (u32) hipLaunchKernelGGL(k_map_finalize<true>, seed_grid(x, nq + 1), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL(k_map_finalize<false>, seed_grid(x, nq + 1), dim3(256), 0, st, f);
+    f.aoff = areq.aoff;
+    f.aqoff = areq.aqoff;
+    f.aqlen = areq.aqlen;
+    with_bool(flags & SAS_LOCATE_U32, [&](auto U32) {
+        hipLaunchKernelGGL(k_map_finalize<decltype(U32)::value>, seed_grid(x, nq + 1), dim3(256), 0, st, f);
+    });
     HIP_TRY(hipGetLastError());
-    // 5. one alignment per read (bytes were validated by the range search when asked for)
-    if (!align) return 0;
-    return sas_align_edit(x, B.qbytes, f.aqoff, f.aqlen, nq, k, f.aoff, o.end, nq, o.start ? o.start : scratch_start,
-                          nullptr, o.nruns, o.runs, st, SAS_DEVICE_PTRS | (flags & SAS_LOCATE_U32));
+    // 5. one alignment per read
+    return align_winners(x, ms.B, areq, nq, k, o, st, flags);
 }
 
-static int map_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                    const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
-                    uint32_t strands, const MapOut& o, void* stream, uint32_t flags) {
+static int map_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint32_t k,
+                    uint64_t max_seed_hits, uint32_t strands, const ReadOut& o, void* stream, uint32_t flags) {
     const std::string w(fn);
     if (strands == 0 || strands > (SAS_MAP_FWD | SAS_MAP_REV))
         SAS_FAIL(EINVAL, w + ": strands must be SAS_MAP_FWD, SAS_MAP_REV or both");
@@ -419,29 +413,17 @@ static int map_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, b
         SAS_FAIL(EINVAL, w + ": " + std::to_string(nq) + " reads on two strands and a text of " + std::to_string(x->n) +
                              " chars do not fit the 64-bit (query, end) sort key: split the batch");
     if (nq == 0) return 0;
-    if (!qbytes || (ragged && (!qoff || !qlen)) || !o.end || !o.dist) SAS_FAIL(EINVAL, w + ": null argument");
+    if (!q.null_ok(nq) || !o.end || !o.dist) SAS_FAIL(EINVAL, w + ": null argument");
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (flags & SAS_DEVICE_PTRS) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        return map_device(x, Q, k, max_seed_hits, strands, o, st, flags);
-    }
+    if (flags & SAS_DEVICE_PTRS) return map_device(x, q.device(nq), k, max_seed_hits, strands, o, st, flags);
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8, stride = 2 * (uint64_t)k + 1;
     HostQueries hq;
     HostOutputs ho;
     MmQueries Q;
-    MapOut d{};
-    TRY(hq.stage("map", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
-    TRY(ho.twin(o.end, nq * esz, "map ends", &d.end));
-    TRY(ho.twin(o.dist, nq, "map distances", &d.dist));
-    TRY(ho.twin(o.start, nq * esz, "map starts", &d.start));
-    TRY(ho.twin(o.strand, nq, "map strands", &d.strand));
-    TRY(ho.twin(o.nbest, nq * 4, "map best counts", &d.nbest));
-    TRY(ho.twin(o.nloci, nq * 4, "map locus counts", &d.nloci));
-    TRY(ho.twin(o.nruns, nq, "map run counts", &d.nruns));
-    TRY(ho.twin(o.runs, nq * stride * 2, "map runs", &d.runs));
-    TRY(ho.twin(o.qflags, nq, "map query flags", &d.qflags));
+    ReadOut d{};
+    TRY(hq.stage("map", q, nq, st, &Q));
+    TRY(twin_reads(ho, o, nq, (flags & SAS_LOCATE_U32) ? 4 : 8, 2 * (uint64_t)k + 1, "map", &d));
     TRY(map_device(x, Q, k, max_seed_hits, strands, d, st, flags | SAS_VALIDATE));
     TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -453,8 +435,9 @@ extern "C" int sas_map_edit(const sas_index* x, const uint8_t* qbytes, const uin
                             void* out_start, uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest,
                             uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
                             void* stream, uint32_t flags) {
-    const MapOut o{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags};
-    return map_impl("sas_map_edit", x, qbytes, true, qoff, qlen, 0, nq, k, max_seed_hits, strands, o, stream, flags);
+    const ReadOut o{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags};
+    return map_impl("sas_map_edit", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, k, max_seed_hits, strands, o, stream,
+                    flags);
 }
 
 extern "C" int sas_map_edit_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
@@ -462,9 +445,9 @@ extern "C" int sas_map_edit_fixed(const sas_index* x, const uint8_t* qbytes, uin
                                   uint8_t* out_dist, uint8_t* out_strand, uint32_t* out_nbest, uint32_t* out_nloci,
                                   uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags, void* stream,
                                   uint32_t flags) {
-    const MapOut o{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags};
-    return map_impl("sas_map_edit_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, max_seed_hits, strands, o,
-                    stream, flags);
+    const ReadOut o{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags};
+    return map_impl("sas_map_edit_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, k, max_seed_hits,
+                    strands, o, stream, flags);
 }
 
 // Device arrays, on the current device (the call takes no index): scratch from its default pool
@@ -498,10 +481,11 @@ static int revcomp_device(const char* fn, const uint8_t* q, const uint64_t* qoff
     return 0;
 }
 
-static int revcomp_impl(const char* fn, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                        const uint32_t* qlen, uint32_t m, uint64_t nq, uint8_t* out_bytes, uint64_t* out_off,
+static int revcomp_impl(const char* fn, const QueryArgs& q, uint64_t nq, uint8_t* out_bytes, uint64_t* out_off,
                         void* stream, uint32_t flags) {
     const std::string w(fn);
+    const uint8_t* qbytes = q.qbytes;
+    const bool ragged = q.ragged;
     const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
     if (ragged && !out_off) SAS_FAIL(EINVAL, w + ": null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -512,28 +496,28 @@ static int revcomp_impl(const char* fn, const uint8_t* qbytes, bool ragged, cons
         }
         return 0;
     }
-    if (ragged && (!qoff || !qlen)) SAS_FAIL(EINVAL, w + ": null argument");
+    if (ragged && (!q.qoff || !q.qlen)) SAS_FAIL(EINVAL, w + ": null argument");
     if (dev) {
         if (!qbytes || !out_bytes) SAS_FAIL(EINVAL, w + ": null argument");
-        return revcomp_device(fn, qbytes, ragged ? qoff : nullptr, qlen, m, nq, out_bytes, out_off, st,
+        return revcomp_device(fn, qbytes, ragged ? q.qoff : nullptr, q.qlen, q.m, nq, out_bytes, out_off, st,
                               (flags & SAS_VALIDATE) != 0);
     }
     // host arrays: copy in, the kernel, copy out (synchronous; bytes always validated)
-    uint64_t total = nq * (uint64_t)m;
+    uint64_t total = nq * (uint64_t)q.m;
     if (ragged) {
         total = 0;
-        for (uint64_t i = 0; i < nq; i++) total += qlen[i];
+        for (uint64_t i = 0; i < nq; i++) total += q.qlen[i];
     }
     if (total && (!qbytes || !out_bytes)) SAS_FAIL(EINVAL, w + ": null argument");
     HostQueries hq;
     HostOutputs ho;
     MmQueries Q;
-    TRY(hq.stage("revcomp", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
+    TRY(hq.stage("revcomp", q, nq, st, &Q));
     uint8_t* dout;
     uint64_t* doff;
     TRY(ho.twin(out_bytes, total, "revcomp output", &dout));  // may be null when there is no byte to write
     TRY(ho.twin(out_off, (nq + 1) * 8, "revcomp offsets", &doff));
-    TRY(revcomp_device(fn, Q.qbytes, Q.qoff, Q.qlen, m, nq, dout, doff, st, true));
+    TRY(revcomp_device(fn, Q.qbytes, Q.qoff, Q.qlen, q.m, nq, dout, doff, st, true));
     TRY(ho.copy_back(st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -541,11 +525,11 @@ static int revcomp_impl(const char* fn, const uint8_t* qbytes, bool ragged, cons
 
 extern "C" int sas_revcomp(const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen, uint64_t nq,
                            uint8_t* out_bytes, uint64_t* out_off, void* stream, uint32_t flags) {
-    return revcomp_impl("sas_revcomp", qbytes, true, qoff, qlen, 0, nq, out_bytes, out_off, stream, flags);
+    return revcomp_impl("sas_revcomp", QueryArgs{qbytes, qoff, qlen, 0, true}, nq, out_bytes, out_off, stream, flags);
 }
 
 extern "C" int sas_revcomp_fixed(const uint8_t* qbytes, uint32_t m, uint64_t nq, uint8_t* out_bytes, void* stream,
                                  uint32_t flags) {
-    return revcomp_impl("sas_revcomp_fixed", qbytes, false, nullptr, nullptr, m, nq, out_bytes, nullptr, stream,
-                        flags);
+    return revcomp_impl("sas_revcomp_fixed", QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, out_bytes, nullptr,
+                        stream, flags);
 }

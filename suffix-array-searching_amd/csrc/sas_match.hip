@@ -246,27 +246,28 @@ static int match_device(const char* fn, const sas_index* x, int mode, const uint
     return 0;
 }
 
-static int match_impl(const char* fn, const sas_index* x, int mode, const uint8_t* qbytes, const uint64_t* qoff,
-                      const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t* out_len, uint64_t* out_pos,
-                      uint64_t* out_lo, uint64_t* out_hi, void* stream, uint32_t flags) {
+// q.ragged: MATCH_RAGGED; q.m: the length of MATCH_FIXED, the cap of MATCH_STATS
+static int match_impl(const char* fn, const sas_index* x, int mode, const QueryArgs& q, uint64_t nq, uint32_t* out_len,
+                      uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi, void* stream, uint32_t flags) {
     const std::string w(fn);
     // no k and no SAS_LOCATE_U32 here; the range search is asked only when it will run
     TRY(seed_index_checks(w, x, 0, flags & SAS_DEVICE_PTRS, stream, out_lo || out_hi));
     if (nq == 0) return 0;
-    if (!qbytes || !out_len || (mode == MATCH_RAGGED && (!qoff || !qlen))) SAS_FAIL(EINVAL, w + ": null argument");
+    if (!q.null_ok(nq) || !out_len) SAS_FAIL(EINVAL, w + ": null argument");
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (flags & SAS_DEVICE_PTRS)
-        return match_device(fn, x, mode, qbytes, qoff, qlen, m, nq, mode == MATCH_RAGGED ? 0 : (m ? m : 1),
+        return match_device(fn, x, mode, q.qbytes, q.qoff, q.qlen, q.m, nq, q.ragged ? 0 : (q.m ? q.m : 1),
                             (flags & SAS_VALIDATE) != 0, out_len, out_pos, out_lo, out_hi, st, flags);
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated).
     // The pattern of MATCH_STATS is copied as plen queries of one char
-    const bool ragged = mode == MATCH_RAGGED;
-    const uint64_t maxlen = ragged ? *std::max_element(qlen, qlen + nq) : m;
+    const bool ragged = q.ragged;
+    const uint32_t m = q.m;
+    const uint64_t maxlen = ragged ? *std::max_element(q.qlen, q.qlen + nq) : m;
     HostQueries hq;
     HostOutputs ho;
     MmQueries Q;
-    TRY(hq.stage("match", qbytes, ragged, qoff, qlen, mode == MATCH_STATS ? 1 : m, nq, st, &Q));
+    TRY(hq.stage("match", QueryArgs{q.qbytes, q.qoff, q.qlen, mode == MATCH_STATS ? 1 : m, ragged}, nq, st, &Q));
     uint32_t* dlen;
     uint64_t *dpos, *dlo, *dhi;
     TRY(ho.twin(out_len, nq * 4, "match lengths out", &dlen));
@@ -283,19 +284,19 @@ static int match_impl(const char* fn, const sas_index* x, int mode, const uint8_
 extern "C" int sas_match(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
                          uint64_t nq, uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi,
                          void* stream, uint32_t flags) {
-    return match_impl("sas_match", x, MATCH_RAGGED, qbytes, qoff, qlen, 0, nq, out_len, out_pos, out_lo, out_hi, stream,
-                      flags);
+    return match_impl("sas_match", x, MATCH_RAGGED, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, out_len, out_pos, out_lo,
+                      out_hi, stream, flags);
 }
 
 extern "C" int sas_match_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t* out_len,
                                uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi, void* stream, uint32_t flags) {
-    return match_impl("sas_match_fixed", x, MATCH_FIXED, qbytes, nullptr, nullptr, m, nq, out_len, out_pos, out_lo,
-                      out_hi, stream, flags);
+    return match_impl("sas_match_fixed", x, MATCH_FIXED, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, out_len,
+                      out_pos, out_lo, out_hi, stream, flags);
 }
 
 extern "C" int sas_match_stats(const sas_index* x, const uint8_t* pattern, uint64_t plen, uint32_t max_len,
                                uint32_t* out_len, uint64_t* out_pos, uint64_t* out_lo, uint64_t* out_hi, void* stream,
                                uint32_t flags) {
-    return match_impl("sas_match_stats", x, MATCH_STATS, pattern, nullptr, nullptr, max_len, plen, out_len, out_pos,
-                      out_lo, out_hi, stream, flags);
+    return match_impl("sas_match_stats", x, MATCH_STATS, QueryArgs{pattern, nullptr, nullptr, max_len, false}, plen,
+                      out_len, out_pos, out_lo, out_hi, stream, flags);
 }

@@ -217,13 +217,12 @@ __global__ __launch_bounds__(MM_BLOCK) void k_mem_verify(MemArgs a) {
     }
 }
 
-template <bool LAY>
+// a kernel of its own for an index with a layout, as k_mm_verify has
 static void mem_launch_verify(const sas_index* x, bool uniq, dim3 grid, hipStream_t st, const MemArgs& a) {
-    with_sa_w(x->sa_w, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        if (uniq) hipLaunchKernelGGL((k_mem_verify<W, LAY, true>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mem_verify<W, LAY, false>), grid, dim3(MM_BLOCK), 0, st, a);
-    });
+    with_sa_w(x->sa_w, [&](auto W) { with_bool(x->lay.nseq != 0, [&](auto LAY) { with_bool(uniq, [&](auto UNIQ) {
+        hipLaunchKernelGGL((k_mem_verify<decltype(W)::value, decltype(LAY)::value, decltype(UNIQ)::value>), grid,
+                           dim3(MM_BLOCK), 0, st, a);
+    }); }); });
 }
 
 struct MemAccept {
@@ -259,19 +258,11 @@ __global__ void k_mem_scatter(const uint32_t* __restrict__ verdict, const uint64
     }
 }
 
-// SAS_MEM_TIMING=1: the verify kernel of every call is timed with HIP events (synchronises);
-// sas_mems_verify_ms returns the calling thread's last figure
-static thread_local double mem_last_verify_ms = -1.0;
-static thread_local uint64_t mem_last_candidates = 0;
-static bool mem_timing() {
-    const char* e = getenv("SAS_MEM_TIMING");
-    return e && e[0] == '1';
-}
+// SAS_MEM_TIMING=1: the verify kernel of every call is timed; sas_mems_verify_ms returns the
+// calling thread's last figure
+static thread_local SeedTiming mem_timing{"SAS_MEM_TIMING"};
 
-extern "C" double sas_mems_verify_ms(uint64_t* candidates) {
-    if (candidates) *candidates = mem_last_candidates;
-    return mem_last_verify_ms;
-}
+extern "C" double sas_mems_verify_ms(uint64_t* candidates) { return mem_timing.get(0, candidates); }
 
 // Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
 struct MemState {
@@ -279,12 +270,6 @@ struct MemState {
     PoolBuf woff, wq, qfl, verdict, cpos, cqpos, scan;
     uint64_t C = 0;
 };
-
-static int mem_zero(uint64_t* out_off, uint64_t nq, uint64_t* out_total, hipStream_t st) {
-    HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
-    if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-    return 0;
-}
 
 // All arrays on the device (out_total may be null).  Host reads: the window total of a ragged
 // batch, and the candidate total
@@ -305,8 +290,7 @@ static int mem_prepare(const sas_index* x, const MmQueries& Q, uint32_t L, uint6
     if (ragged) {
         W.woff = s.woff.as<uint64_t>();
         TRY(pool_scan(pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
-        HIP_TRY(hipMemcpyAsync(&W.nw, W.woff + nq, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        TRY(seed_read_total(W.woff + nq, st, &W.nw));
         TRY(s.wq.alloc(pool, W.nw * 8, st));
     } else {
         W.nw = nq * W.per;
@@ -323,12 +307,10 @@ static int mem_prepare(const sas_index* x, const MmQueries& Q, uint32_t L, uint6
     HIP_TRY(hipGetLastError());
     TRY(seed_offsets(x, nw, st, s.seed));
     uint64_t* coff = s.seed.coff.as<uint64_t>();
-    HIP_TRY(hipMemcpyAsync(&s.C, coff + nw, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(seed_read_total(coff + nw, st, &s.C));
     const uint64_t C = s.C;
-    mem_last_candidates = C;
-    mem_last_verify_ms = -1.0;
-    if (C == 0) return mem_zero(out_off, nq, out_total, st);
+    mem_timing.reset(C);
+    if (C == 0) return seed_nothing(out_off, nq, out_total, st);
     TRY(s.verdict.alloc(pool, (C + 1) * 4, st));
     TRY(s.cpos.alloc(pool, C * 8, st));
     TRY(s.cqpos.alloc(pool, C * 4, st));
@@ -349,17 +331,11 @@ static int mem_prepare(const sas_index* x, const MmQueries& Q, uint32_t L, uint6
     a.verdict = s.verdict.as<uint32_t>();
     a.cpos = s.cpos.as<uint64_t>();
     a.cqpos = s.cqpos.as<uint32_t>();
-    uint64_t blocks = (C + MM_T - 1) / MM_T;
-    if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
-    const dim3 vgrid((unsigned)tile_grid(blocks));
-    const bool uniq = (flags & SAS_MEM_UNIQUE) != 0;
-    SeedTimer timer(mem_timing(), st);
+    SeedTimer timer(mem_timing.on(), st);
     TRY(timer.start());
-    // a kernel of its own for an index with a layout, as k_mm_verify has
-    if (x->lay.nseq) mem_launch_verify<true>(x, uniq, vgrid, st, a);
-    else mem_launch_verify<false>(x, uniq, vgrid, st, a);
+    mem_launch_verify(x, (flags & SAS_MEM_UNIQUE) != 0, seed_verify_grid(C), st, a);
     HIP_TRY(hipGetLastError());
-    TRY(timer.stop(&mem_last_verify_ms));
+    TRY(timer.stop(&mem_timing.ms[0]));
     TRY(pool_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint32_t>(), MemAccept{}),
                   s.scan.as<uint64_t>(), C + 1));
     hipLaunchKernelGGL(k_mem_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, W, coff, s.scan.as<uint64_t>(), nq,
@@ -372,88 +348,48 @@ static int mem_scatter(const sas_index* x, MemState& s, uint32_t* out_qpos, void
                        uint64_t capacity, hipStream_t st, uint32_t flags) {
     if (s.C == 0 || capacity == 0) return 0;
     const dim3 grid(std::min(grid_for(s.C), (unsigned)x->num_cus * 8));
-    if (flags & SAS_LOCATE_U32)
-        hipLaunchKernelGGL(k_mem_scatter<true>, grid, dim3(256), 0, st, s.verdict.as<uint32_t>(),
+    with_bool(flags & SAS_LOCATE_U32, [&](auto U32) {
+        hipLaunchKernelGGL(k_mem_scatter<decltype(U32)::value>, grid, dim3(256), 0, st, s.verdict.as<uint32_t>(),
                            s.scan.as<uint64_t>(), s.cpos.as<uint64_t>(), s.cqpos.as<uint32_t>(), s.C, out_qpos, out_tpos,
                            out_len, capacity);
-    else
-        hipLaunchKernelGGL(k_mem_scatter<false>, grid, dim3(256), 0, st, s.verdict.as<uint32_t>(),
-                           s.scan.as<uint64_t>(), s.cpos.as<uint64_t>(), s.cqpos.as<uint32_t>(), s.C, out_qpos, out_tpos,
-                           out_len, capacity);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-static int mems_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                     const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t min_len, uint64_t max_hits,
-                     uint64_t* out_off, uint32_t* out_qpos, void* out_tpos, uint32_t* out_len, uint8_t* out_qflags,
-                     uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
+static int mems_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint32_t min_len,
+                     uint64_t max_hits, uint64_t* out_off, uint32_t* out_qpos, void* out_tpos, uint32_t* out_len,
+                     uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
     const std::string w(fn);
     if (min_len == 0) SAS_FAIL(EINVAL, w + ": min_len must be at least 1");
     TRY(seed_index_checks(w, x, 0, flags, stream));
-    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
-    if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) ||
-        (capacity && (!out_qpos || !out_tpos || !out_len)) || (!dev && !out_total))
-        SAS_FAIL(EINVAL, w + ": null argument");
-    HIP_TRY(hipSetDevice(x->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (nq == 0) {
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(out_off, 0, 8, st));
-            if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-        } else {
-            out_off[0] = 0;
-            *out_total = 0;
-        }
-        return 0;
-    }
     MemState s;
-    if (dev) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        TRY(mem_prepare(x, Q, min_len, max_hits, out_off, out_qflags, out_total, st, flags, s));
-        return mem_scatter(x, s, out_qpos, out_tpos, out_len, capacity, st, flags);
-    }
-    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    HostQueries hq;
-    HostOutputs ho;
-    MmQueries Q;
-    TRY(hq.stage("mems", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
-    uint64_t* doff;
-    uint8_t* dfl;
-    TRY(ho.twin(out_off, (nq + 1) * 8, "mems result offsets", &doff));
-    TRY(ho.twin(out_qflags, nq, "mems query flags", &dfl));
-    TRY(mem_prepare(x, Q, min_len, max_hits, doff, dfl, nullptr, st, flags | SAS_VALIDATE, s));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t total = out_off[nq];
-    *out_total = total;
-    if (total > capacity)
-        SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " matches, capacity " + std::to_string(capacity) +
-                             " (size the outputs from *out_total and call again)");
-    if (total == 0) return 0;
-    uint32_t *dqpos, *dlen;
-    void* dtpos;
-    TRY(ho.twin(out_qpos, total * 4, "mems query offsets", &dqpos));
-    TRY(ho.twin(out_tpos, total * ((flags & SAS_LOCATE_U32) ? 4 : 8), "mems text positions", &dtpos));
-    TRY(ho.twin(out_len, total * 4, "mems lengths", &dlen));
-    TRY(mem_scatter(x, s, dqpos, dtpos, dlen, total, st, flags));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    const ListOut outs[] = {{out_qpos, 4, "mems query offsets", true},
+                            {out_tpos, (flags & SAS_LOCATE_U32) ? 4u : 8u, "mems text positions", true},
+                            {out_len, 4, "mems lengths", true}};
+    return seed_list_call(
+        {fn, "mems", "matches", "the outputs", nullptr}, x, q, nq, out_off, out_qflags, outs, 3, capacity, out_total, stream, flags,
+        [&](const MmQueries& Q, uint64_t* off, uint8_t* qfl, uint64_t* total, hipStream_t st, uint32_t fl) {
+            return mem_prepare(x, Q, min_len, max_hits, off, qfl, total, st, fl, s);
+        },
+        [&](void* const* out, uint64_t cap, hipStream_t st) {
+            return mem_scatter(x, s, static_cast<uint32_t*>(out[0]), out[1], static_cast<uint32_t*>(out[2]), cap, st,
+                               flags);
+        });
 }
 
 extern "C" int sas_mems(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff, const uint32_t* qlen,
                         uint64_t nq, uint32_t min_len, uint64_t max_hits, uint64_t* out_off, uint32_t* out_qpos,
                         void* out_tpos, uint32_t* out_len, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
                         void* stream, uint32_t flags) {
-    return mems_impl("sas_mems", x, qbytes, true, qoff, qlen, 0, nq, min_len, max_hits, out_off, out_qpos, out_tpos,
-                     out_len, out_qflags, capacity, out_total, stream, flags);
+    return mems_impl("sas_mems", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, min_len, max_hits, out_off, out_qpos,
+                     out_tpos, out_len, out_qflags, capacity, out_total, stream, flags);
 }
 
 extern "C" int sas_mems_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t min_len,
                               uint64_t max_hits, uint64_t* out_off, uint32_t* out_qpos, void* out_tpos,
                               uint32_t* out_len, uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total,
                               void* stream, uint32_t flags) {
-    return mems_impl("sas_mems_fixed", x, qbytes, false, nullptr, nullptr, m, nq, min_len, max_hits, out_off, out_qpos,
-                     out_tpos, out_len, out_qflags, capacity, out_total, stream, flags);
+    return mems_impl("sas_mems_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, min_len, max_hits, out_off,
+                     out_qpos, out_tpos, out_len, out_qflags, capacity, out_total, stream, flags);
 }

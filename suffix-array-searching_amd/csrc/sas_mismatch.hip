@@ -154,13 +154,12 @@ __global__ __launch_bounds__(MM_BLOCK) void k_mm_verify(MmArgs a) {
     }
 }
 
-template <bool LAY>
+// a kernel of its own for an index with a layout: without one the parent's instructions run
 static void mm_launch_verify(const sas_index* x, bool pre, dim3 grid, hipStream_t st, const MmArgs& a) {
-    with_sa_w(x->sa_w, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        if (pre) hipLaunchKernelGGL((k_mm_verify<W, true, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_mm_verify<W, false, LAY>), grid, dim3(MM_BLOCK), 0, st, a);
-    });
+    with_sa_w(x->sa_w, [&](auto W) { with_bool(pre, [&](auto PRE) { with_bool(x->lay.nseq != 0, [&](auto LAY) {
+        hipLaunchKernelGGL((k_mm_verify<decltype(W)::value, decltype(PRE)::value, decltype(LAY)::value>), grid,
+                           dim3(MM_BLOCK), 0, st, a);
+    }); }); });
 }
 
 struct MmAccept {
@@ -199,19 +198,11 @@ static bool mm_prepacked() {
     return e && strcmp(e, "packed") == 0;
 }
 
-// SAS_MM_TIMING=1: the verify kernel of every call is timed with HIP events (synchronises);
-// sas_locate_mismatch_verify_ms returns the calling thread's last figure
-static thread_local double mm_last_verify_ms = -1.0;
-static thread_local uint64_t mm_last_candidates = 0;
-static bool mm_timing() {
-    const char* e = getenv("SAS_MM_TIMING");
-    return e && e[0] == '1';
-}
+// SAS_MM_TIMING=1: the verify kernel of every call is timed; sas_locate_mismatch_verify_ms
+// returns the calling thread's last figure
+static thread_local SeedTiming mm_timing{"SAS_MM_TIMING"};
 
-extern "C" double sas_locate_mismatch_verify_ms(uint64_t* candidates) {
-    if (candidates) *candidates = mm_last_candidates;
-    return mm_last_verify_ms;
-}
+extern "C" double sas_locate_mismatch_verify_ms(uint64_t* candidates) { return mm_timing.get(0, candidates); }
 
 // Steps 1..6 up to the offsets; the scratch the scatter needs stays in the state
 struct MmState {
@@ -240,16 +231,10 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
         TRY(pool_scan(pool, st, s.woff.as<uint64_t>(), s.woff.as<uint64_t>(), nq + 1));
         if (Q.qoff) HIP_TRY(hipMemcpyAsync(&words, s.woff.as<uint64_t>() + nq, 8, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipMemcpyAsync(&s.C, coff + np, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(seed_read_total(coff + np, st, &s.C));
     const uint64_t C = s.C;
-    mm_last_candidates = C;
-    mm_last_verify_ms = -1.0;
-    if (C == 0) {
-        HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
-        if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-        return 0;
-    }
+    mm_timing.reset(C);
+    if (C == 0) return seed_nothing(out_off, nq, out_total, st);
     if (pre) {
         TRY(s.qw.alloc(pool, words * 8, st));
         hipLaunchKernelGGL(k_mm_prepack, seed_grid(x, nq), dim3(256), 0, st, Q, s.woff.as<uint64_t>(),
@@ -275,17 +260,12 @@ static int mm_prepare(const sas_index* x, const MmQueries& Q, uint32_t k, uint64
     a.qw = s.qw.as<uint64_t>();
     a.verdict = s.verdict.as<uint8_t>();
     a.cpos = s.cpos.as<uint64_t>();
-    uint64_t blocks = (C + MM_T - 1) / MM_T;
-    if (blocks > MM_MAX_GRID) blocks = MM_MAX_GRID;
-    const dim3 vgrid((unsigned)tile_grid(blocks));
-    SeedTimer timer(mm_timing(), st);
-    TRY(timer.start());
-    // a kernel of its own for an index with a layout: without one the parent's instructions run
     a.lay = x->lay;
-    if (x->lay.nseq) mm_launch_verify<true>(x, pre, vgrid, st, a);
-    else mm_launch_verify<false>(x, pre, vgrid, st, a);
+    SeedTimer timer(mm_timing.on(), st);
+    TRY(timer.start());
+    mm_launch_verify(x, pre, seed_verify_grid(C), st, a);
     HIP_TRY(hipGetLastError());
-    TRY(timer.stop(&mm_last_verify_ms));
+    TRY(timer.stop(&mm_timing.ms[0]));
     TRY(pool_scan(pool, st, rocprim::make_transform_iterator(s.verdict.as<uint8_t>(), MmAccept{}),
                 s.scan.as<uint64_t>(), C + 1));
     hipLaunchKernelGGL(k_mm_offsets, seed_grid(x, nq + 1), dim3(256), 0, st, coff, s.scan.as<uint64_t>(), nq, kp1,
@@ -298,84 +278,45 @@ static int mm_scatter(const sas_index* x, MmState& s, void* out_pos, uint8_t* ou
                       hipStream_t st, uint32_t flags) {
     if (s.C == 0 || capacity == 0) return 0;
     const dim3 grid(std::min(grid_for(s.C), (unsigned)x->num_cus * 8));
-    if (flags & SAS_LOCATE_U32)
-        hipLaunchKernelGGL(k_mm_scatter<true>, grid, dim3(256), 0, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(),
-                           s.cpos.as<uint64_t>(), s.C, out_pos, out_dist, capacity);
-    else
-        hipLaunchKernelGGL(k_mm_scatter<false>, grid, dim3(256), 0, st, s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(),
-                           s.cpos.as<uint64_t>(), s.C, out_pos, out_dist, capacity);
+    with_bool(flags & SAS_LOCATE_U32, [&](auto U32) {
+        hipLaunchKernelGGL(k_mm_scatter<decltype(U32)::value>, grid, dim3(256), 0, st,
+                           s.verdict.as<uint8_t>(), s.scan.as<uint64_t>(), s.cpos.as<uint64_t>(), s.C, out_pos, out_dist,
+                           capacity);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-static int mismatch_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-                         const uint32_t* qlen, uint32_t m, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
-                         uint64_t* out_off, void* out_pos, uint8_t* out_dist, uint8_t* out_qflags, uint64_t capacity,
-                         uint64_t* out_total, void* stream, uint32_t flags) {
+static int mismatch_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t nq, uint32_t k,
+                         uint64_t max_seed_hits, uint64_t* out_off, void* out_pos, uint8_t* out_dist,
+                         uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
     const std::string w(fn);
     TRY(seed_index_checks(w, x, k, flags, stream));
-    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
-    if (!out_off || (nq && (!qbytes || (ragged && (!qoff || !qlen)))) || (capacity && !out_pos) ||
-        (!dev && !out_total))
-        SAS_FAIL(EINVAL, w + ": null argument");
-    HIP_TRY(hipSetDevice(x->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (nq == 0) {
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(out_off, 0, 8, st));
-            if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
-        } else {
-            out_off[0] = 0;
-            *out_total = 0;
-        }
-        return 0;
-    }
     MmState s;
-    if (dev) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        TRY(mm_prepare(x, Q, k, max_seed_hits, out_off, out_qflags, out_total, st, flags, s));
-        return mm_scatter(x, s, out_pos, out_dist, capacity, st, flags);
-    }
-    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
-    HostQueries hq;
-    HostOutputs ho;
-    MmQueries Q;
-    TRY(hq.stage("mismatch", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
-    uint64_t* doff;
-    uint8_t* dfl;
-    TRY(ho.twin(out_off, (nq + 1) * 8, "mismatch result offsets", &doff));
-    TRY(ho.twin(out_qflags, nq, "mismatch query flags", &dfl));
-    TRY(mm_prepare(x, Q, k, max_seed_hits, doff, dfl, nullptr, st, flags | SAS_VALIDATE, s));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t total = out_off[nq];
-    *out_total = total;
-    if (total > capacity)
-        SAS_FAIL(ENOSPC, w + ": " + std::to_string(total) + " positions, capacity " + std::to_string(capacity) +
-                             " (size out_pos from *out_total and call again)");
-    if (total == 0) return 0;
-    void* dpos;
-    uint8_t* ddist;
-    TRY(ho.twin(out_pos, total * ((flags & SAS_LOCATE_U32) ? 4 : 8), "mismatch positions", &dpos));
-    TRY(ho.twin(out_dist, total, "mismatch distances", &ddist));
-    TRY(mm_scatter(x, s, dpos, ddist, total, st, flags));
-    TRY(ho.copy_back(st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    const ListOut outs[] = {{out_pos, (flags & SAS_LOCATE_U32) ? 4u : 8u, "mismatch positions", true},
+                            {out_dist, 1, "mismatch distances", false}};
+    return seed_list_call(
+        {fn, "mismatch", "positions", "out_pos", nullptr}, x, q, nq, out_off, out_qflags, outs, 2, capacity, out_total, stream, flags,
+        [&](const MmQueries& Q, uint64_t* off, uint8_t* qfl, uint64_t* total, hipStream_t st, uint32_t fl) {
+            return mm_prepare(x, Q, k, max_seed_hits, off, qfl, total, st, fl, s);
+        },
+        [&](void* const* out, uint64_t cap, hipStream_t st) {
+            return mm_scatter(x, s, out[0], static_cast<uint8_t*>(out[1]), cap, st, flags);
+        });
 }
 
 extern "C" int sas_locate_mismatch(const sas_index* x, const uint8_t* qbytes, const uint64_t* qoff,
                                    const uint32_t* qlen, uint64_t nq, uint32_t k, uint64_t max_seed_hits,
                                    uint64_t* out_off, void* out_pos, uint8_t* out_dist, uint8_t* out_qflags,
                                    uint64_t capacity, uint64_t* out_total, void* stream, uint32_t flags) {
-    return mismatch_impl("sas_locate_mismatch", x, qbytes, true, qoff, qlen, 0, nq, k, max_seed_hits, out_off, out_pos,
-                         out_dist, out_qflags, capacity, out_total, stream, flags);
+    return mismatch_impl("sas_locate_mismatch", x, QueryArgs{qbytes, qoff, qlen, 0, true}, nq, k, max_seed_hits, out_off,
+                         out_pos, out_dist, out_qflags, capacity, out_total, stream, flags);
 }
 
 extern "C" int sas_locate_mismatch_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t nq, uint32_t k,
                                          uint64_t max_seed_hits, uint64_t* out_off, void* out_pos, uint8_t* out_dist,
                                          uint8_t* out_qflags, uint64_t capacity, uint64_t* out_total, void* stream,
                                          uint32_t flags) {
-    return mismatch_impl("sas_locate_mismatch_fixed", x, qbytes, false, nullptr, nullptr, m, nq, k, max_seed_hits,
-                         out_off, out_pos, out_dist, out_qflags, capacity, out_total, stream, flags);
+    return mismatch_impl("sas_locate_mismatch_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, nq, k,
+                         max_seed_hits, out_off, out_pos, out_dist, out_qflags, capacity, out_total, stream, flags);
 }

@@ -522,15 +522,10 @@ int pair_finish(const sas_index* x, const PairCall& c, PairState& ps, const uint
     const MmQueries& B = ms.B;
     const EdState& s = ms.s;
     const uint64_t nq = B.nq / 2, np = nq / 2;
-    hipMemPool_t pool;
-    TRY(sas_scratch_pool(x, &pool));
     PoolBuf &pslots = ps.pslots, &meta = ps.meta, &lkey = ps.lkey, &ldist = ps.ldist;
-    PoolBuf areq;
     // 4. the records and the alignment request
-    const bool align = o.start || o.nruns || o.runs;
-    const bool u32 = (flags & SAS_LOCATE_U32) != 0;
-    const uint64_t esz = u32 ? 4 : 8;
-    TRY(areq.alloc(pool, (nq + 1) * 8 + nq * 8 + nq * 4 + (o.start ? 0 : nq * esz), st));
+    AlignReq areq;
+    TRY(areq.alloc(x, nq, o.start, flags, st));
     PairFin f{};
     f.B = B;
     f.np = np;
@@ -551,18 +546,15 @@ int pair_finish(const sas_index* x, const PairCall& c, PairState& ps, const uint
     f.pcnt = f.pmin + np;
     f.pbest = f.pmin + 2 * np;
     f.o = o;
-    f.aoff = areq.as<uint64_t>();
-    f.aqoff = f.aoff + nq + 1;
-    void* scratch_start = f.aqoff + nq;                  // 8-byte aligned; unused when out_start is given
-    f.aqlen = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch_start) + (o.start ? 0 : nq * esz));
-    if (u32) hipLaunchKernelGGL((k_pair_finalize<true, RESCUE>), seed_grid(x, np + 1), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL((k_pair_finalize<false, RESCUE>), seed_grid(x, np + 1), dim3(256), 0, st, f);
+    f.aoff = areq.aoff;
+    f.aqoff = areq.aqoff;
+    f.aqlen = areq.aqlen;
+    with_bool(flags & SAS_LOCATE_U32, [&](auto U32) {
+        hipLaunchKernelGGL((k_pair_finalize<decltype(U32)::value, RESCUE>), seed_grid(x, np + 1), dim3(256), 0, st, f);
+    });
     HIP_TRY(hipGetLastError());
-    // 5. one alignment per read (bytes were validated by the range search when asked for)
-    if (!align) return 0;
-    return sas_align_edit(x, B.qbytes, f.aqoff, f.aqlen, nq, RESCUE ? c.k_rescue : c.k, f.aoff, o.end, nq,
-                          o.start ? o.start : scratch_start, nullptr, o.nruns, o.runs, st,
-                          SAS_DEVICE_PTRS | (flags & SAS_LOCATE_U32));
+    // 5. one alignment per read
+    return align_winners(x, B, areq, nq, RESCUE ? c.k_rescue : c.k, o, st, flags);
 }
 
 template int pair_finish<false>(const sas_index*, const PairCall&, PairState&, const uint64_t*, const uint64_t*,
@@ -570,9 +562,8 @@ template int pair_finish<false>(const sas_index*, const PairCall&, PairState&, c
 template int pair_finish<true>(const sas_index*, const PairCall&, PairState&, const uint64_t*, const uint64_t*,
                                const PairOut&, hipStream_t, uint32_t);
 
-int pairs_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool ragged, const uint64_t* qoff,
-               const uint32_t* qlen, uint32_t m, uint64_t np, const PairCall& c, PairDevice device, const PairOut& o,
-               void* stream, uint32_t flags) {
+int pairs_impl(const char* fn, const sas_index* x, const QueryArgs& q, uint64_t np, const PairCall& c, PairDevice device,
+               const PairOut& o, void* stream, uint32_t flags) {
     const std::string w(fn);
     const uint32_t k = c.k, min_frag = c.min_frag, max_frag = c.max_frag;
     if (min_frag > max_frag) SAS_FAIL(EINVAL, w + ": min_frag must not exceed max_frag");
@@ -587,30 +578,19 @@ int pairs_impl(const char* fn, const sas_index* x, const uint8_t* qbytes, bool r
         SAS_FAIL(EINVAL, w + ": " + std::to_string(np) + " pairs on two strands and a text of " + std::to_string(x->n) +
                              " chars do not fit the 64-bit (query, end) sort key: split the batch");
     if (np == 0) return 0;
-    if (!qbytes || (ragged && (!qoff || !qlen)) || !o.end || !o.dist) SAS_FAIL(EINVAL, w + ": null argument");
+    const uint64_t nq = 2 * np;
+    if (!q.null_ok(nq) || !o.end || !o.dist) SAS_FAIL(EINVAL, w + ": null argument");
     HIP_TRY(hipSetDevice(x->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint64_t nq = 2 * np;
-    if (flags & SAS_DEVICE_PTRS) {
-        const MmQueries Q{qbytes, ragged ? qoff : nullptr, qlen, m, nq};
-        return device(x, Q, c, o, st, flags);
-    }
+    if (flags & SAS_DEVICE_PTRS) return device(x, q.device(nq), c, o, st, flags);
     // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
     const uint64_t esz = (flags & SAS_LOCATE_U32) ? 4 : 8, stride = 2 * (uint64_t)(c.rescue ? c.k_rescue : k) + 1;
     HostQueries hq;
     HostOutputs ho;
     MmQueries Q;
     PairOut d{};
-    TRY(hq.stage("pair", qbytes, ragged, qoff, qlen, m, nq, st, &Q));
-    TRY(ho.twin(o.end, nq * esz, "pair ends", &d.end));
-    TRY(ho.twin(o.dist, nq, "pair distances", &d.dist));
-    TRY(ho.twin(o.start, nq * esz, "pair starts", &d.start));
-    TRY(ho.twin(o.strand, nq, "pair strands", &d.strand));
-    TRY(ho.twin(o.nbest, nq * 4, "pair best counts", &d.nbest));
-    TRY(ho.twin(o.nloci, nq * 4, "pair locus counts", &d.nloci));
-    TRY(ho.twin(o.nruns, nq, "pair run counts", &d.nruns));
-    TRY(ho.twin(o.runs, nq * stride * 2, "pair runs", &d.runs));
-    TRY(ho.twin(o.qflags, nq, "pair query flags", &d.qflags));
+    TRY(hq.stage("pair", q, nq, st, &Q));
+    TRY(twin_reads(ho, o, nq, esz, stride, "pair", &d));
     TRY(ho.twin(o.pflags, np, "pair flags", &d.pflags));
     TRY(ho.twin(o.npairs, np * 4, "pair candidate counts", &d.npairs));
     TRY(ho.twin(o.nbestpairs, np * 4, "pair best candidate counts", &d.nbestpairs));
@@ -635,10 +615,11 @@ extern "C" int sas_map_pairs(const sas_index* x, const uint8_t* qbytes, const ui
                              uint8_t* out_strand, uint32_t* out_nbest, uint32_t* out_nloci, uint8_t* out_nruns,
                              uint16_t* out_runs, uint8_t* out_qflags, uint8_t* out_pflags, uint32_t* out_npairs,
                              uint32_t* out_nbestpairs, void* stream, uint32_t flags) {
-    const PairOut o{out_end,   out_start, out_dist,   out_strand, out_nbest,      out_nloci, out_nruns,
-                    out_runs,  out_qflags, out_pflags, out_npairs, out_nbestpairs, nullptr};
+    const PairOut o{{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags},
+                    out_pflags, out_npairs, out_nbestpairs, nullptr};
     const PairCall c{k, k, max_seed_hits, min_frag, max_frag, 0, false};
-    return pairs_impl("sas_map_pairs", x, qbytes, true, qoff, qlen, 0, npairs, c, pairs_device, o, stream, flags);
+    return pairs_impl("sas_map_pairs", x, QueryArgs{qbytes, qoff, qlen, 0, true}, npairs, c, pairs_device, o, stream,
+                      flags);
 }
 
 extern "C" int sas_map_pairs_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t npairs, uint32_t k,
@@ -647,9 +628,9 @@ extern "C" int sas_map_pairs_fixed(const sas_index* x, const uint8_t* qbytes, ui
                                    uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs, uint8_t* out_qflags,
                                    uint8_t* out_pflags, uint32_t* out_npairs, uint32_t* out_nbestpairs, void* stream,
                                    uint32_t flags) {
-    const PairOut o{out_end,   out_start, out_dist,   out_strand, out_nbest,      out_nloci, out_nruns,
-                    out_runs,  out_qflags, out_pflags, out_npairs, out_nbestpairs, nullptr};
+    const PairOut o{{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags},
+                    out_pflags, out_npairs, out_nbestpairs, nullptr};
     const PairCall c{k, k, max_seed_hits, min_frag, max_frag, 0, false};
-    return pairs_impl("sas_map_pairs_fixed", x, qbytes, false, nullptr, nullptr, m, npairs, c, pairs_device, o, stream,
-                      flags);
+    return pairs_impl("sas_map_pairs_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, npairs, c, pairs_device,
+                      o, stream, flags);
 }

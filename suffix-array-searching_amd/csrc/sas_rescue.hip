@@ -313,15 +313,9 @@ static int rescue_device(const sas_index* x, const MmQueries& Q, const PairCall&
         const uint64_t upper = P * (uint64_t)a.cpa;
         const dim3 rgrid(tile_grid(std::min(grid_for(upper, RS_BLOCK), (unsigned)x->num_cus * 8)));
         a.lay = x->lay;
-        if (x->lay.nseq) {
-            if (B.qoff) hipLaunchKernelGGL((k_pair_rescue<0, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
-            else if (B.m <= 64) hipLaunchKernelGGL((k_pair_rescue<1, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
-            else if (B.m <= 128) hipLaunchKernelGGL((k_pair_rescue<2, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_pair_rescue<4, true>), rgrid, dim3(RS_BLOCK), 0, st, a);
-        } else if (B.qoff) hipLaunchKernelGGL((k_pair_rescue<0, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
-        else if (B.m <= 64) hipLaunchKernelGGL((k_pair_rescue<1, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
-        else if (B.m <= 128) hipLaunchKernelGGL((k_pair_rescue<2, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_pair_rescue<4, false>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        with_ed_words(B, [&](auto NW) { with_bool(x->lay.nseq != 0, [&](auto LAY) {
+            hipLaunchKernelGGL((k_pair_rescue<decltype(NW)::value, decltype(LAY)::value>), rgrid, dim3(RS_BLOCK), 0, st, a);
+        }); });
         HIP_TRY(hipGetLastError());
     }
     return pair_finish<true>(x, c, ps, rmin, rcnt, o, st, flags);
@@ -334,11 +328,11 @@ extern "C" int sas_map_pairs_rescue(const sas_index* x, const uint8_t* qbytes, c
                                     uint32_t* out_nbest, uint32_t* out_nloci, uint8_t* out_nruns, uint16_t* out_runs,
                                     uint8_t* out_qflags, uint8_t* out_pflags, uint32_t* out_npairs,
                                     uint32_t* out_nbestpairs, uint32_t* out_nrescue, void* stream, uint32_t flags) {
-    const PairOut o{out_end,  out_start,  out_dist,   out_strand, out_nbest,      out_nloci,  out_nruns,
-                    out_runs, out_qflags, out_pflags, out_npairs, out_nbestpairs, out_nrescue};
+    const PairOut o{{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags},
+                    out_pflags, out_npairs, out_nbestpairs, out_nrescue};
     const PairCall c{k, k_rescue, max_seed_hits, min_frag, max_frag, max_anchors, true};
-    return pairs_impl("sas_map_pairs_rescue", x, qbytes, true, qoff, qlen, 0, npairs, c, rescue_device, o, stream,
-                      flags);
+    return pairs_impl("sas_map_pairs_rescue", x, QueryArgs{qbytes, qoff, qlen, 0, true}, npairs, c, rescue_device, o,
+                      stream, flags);
 }
 
 extern "C" int sas_map_pairs_rescue_fixed(const sas_index* x, const uint8_t* qbytes, uint32_t m, uint64_t npairs,
@@ -349,9 +343,9 @@ extern "C" int sas_map_pairs_rescue_fixed(const sas_index* x, const uint8_t* qby
                                           uint8_t* out_qflags, uint8_t* out_pflags, uint32_t* out_npairs,
                                           uint32_t* out_nbestpairs, uint32_t* out_nrescue, void* stream,
                                           uint32_t flags) {
-    const PairOut o{out_end,  out_start,  out_dist,   out_strand, out_nbest,      out_nloci,  out_nruns,
-                    out_runs, out_qflags, out_pflags, out_npairs, out_nbestpairs, out_nrescue};
+    const PairOut o{{out_end, out_start, out_dist, out_strand, out_nbest, out_nloci, out_nruns, out_runs, out_qflags},
+                    out_pflags, out_npairs, out_nbestpairs, out_nrescue};
     const PairCall c{k, k_rescue, max_seed_hits, min_frag, max_frag, max_anchors, true};
-    return pairs_impl("sas_map_pairs_rescue_fixed", x, qbytes, false, nullptr, nullptr, m, npairs, c, rescue_device, o,
-                      stream, flags);
+    return pairs_impl("sas_map_pairs_rescue_fixed", x, QueryArgs{qbytes, nullptr, nullptr, m, false}, npairs, c,
+                      rescue_device, o, stream, flags);
 }

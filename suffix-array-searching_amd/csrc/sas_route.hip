@@ -68,7 +68,7 @@ static int route_impl(const sas_index* x, const uint64_t* splitter_pos, uint32_t
     if (!dev) {  // host arrays: copy in, the kernel, copy out (synchronous; bytes not validated)
         TRY(host_copy_in(bsp, splitter_pos, nsplit * 8, "route splitters"));
         dsp = bsp.as<uint64_t>();
-        TRY(hq.stage("route", qbytes, qoff != nullptr, qoff, qlen, m, nq, st, &Q));
+        TRY(hq.stage("route", QueryArgs{qbytes, qoff, qlen, m, qoff != nullptr}, nq, st, &Q));
         TRY(ho.twin(out_shard, nq * 4, "route shards", &dout));
     }
     uint64_t blocks = (nq + 255) / 256;

@@ -456,7 +456,7 @@ struct DirectCall {
             qw = qw_for(maxlen);
             a.m_max = maxlen ? maxlen : 1;
             MmQueries Q;
-            TRY(hq.stage("search", io.qbytes, ragged, io.qoff, io.qlen, a.m_fixed, nq, st, &Q));
+            TRY(hq.stage("search", QueryArgs{io.qbytes, io.qoff, io.qlen, a.m_fixed, ragged}, nq, st, &Q));
             a.qbytes = Q.qbytes;
             a.qoff = Q.qoff;
             a.qlen = Q.qlen;

@@ -1,6 +1,6 @@
 // seed_verify.hip -- the stages that every seed-and-verify call runs, defined once
-// (seed_verify.hpp declares them): the index preconditions and the seed stage up to the
-// candidate offsets.
+// (seed_verify.hpp declares them): the index preconditions, the seed stage up to the candidate
+// offsets and the call path of the two-pass calls.
 #include "seed_verify.hpp"
 
 static_assert(SAS_MM_TRUNCATED == SAS_ED_TRUNCATED && SAS_MM_SHORT == SAS_ED_SHORT,
@@ -94,4 +94,50 @@ int seed_candidates(const sas_index* x, const MmQueries& Q, uint32_t k, uint64_t
                        s.skip.as<uint16_t>(), qflags);
     HIP_TRY(hipGetLastError());
     return seed_offsets(x, np, st, s);
+}
+
+int seed_list_call(const ListCall& c, const sas_index* x, const QueryArgs& q, uint64_t nq, uint64_t* out_off,
+                   uint8_t* out_qflags, const ListOut* outs, int nouts, uint64_t capacity, uint64_t* out_total,
+                   void* stream, uint32_t flags, const ListPrepare& prepare, const ListScatter& scatter) {
+    const bool dev = (flags & SAS_DEVICE_PTRS) != 0;
+    const std::string fn(c.fn);
+    if (nouts > HostOutputs::MAX) SAS_FAIL(EINVAL, fn + ": more payload outputs than HostOutputs holds");
+    bool null = !out_off || !q.null_ok(nq) || (!dev && !out_total);
+    void* out[HostOutputs::MAX];
+    for (int i = 0; i < nouts; i++) {
+        null = null || (capacity && outs[i].required && !outs[i].ptr);
+        out[i] = outs[i].ptr;
+    }
+    if (null) SAS_FAIL(EINVAL, fn + ": null argument");
+    if (c.check) TRY(c.check());
+    HIP_TRY(hipSetDevice(x->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (nq == 0) {
+        if (dev) return seed_nothing(out_off, 0, out_total, st);
+        out_off[0] = 0;
+        *out_total = 0;
+        return 0;
+    }
+    if (dev) {
+        TRY(prepare(q.device(nq), out_off, out_qflags, out_total, st, flags));
+        return scatter(out, capacity, st);
+    }
+    // host arrays: copy in, the device path, copy out (synchronous; bytes always validated)
+    const std::string l(c.label);
+    HostQueries hq;
+    HostOutputs ho;
+    MmQueries Q;
+    TRY(hq.stage(c.label, q, nq, st, &Q));
+    uint64_t *doff, total;
+    uint8_t* dfl;
+    TRY(ho.twin(out_off, (nq + 1) * 8, (l + " result offsets").c_str(), &doff));
+    TRY(ho.twin(out_qflags, nq, (l + " query flags").c_str(), &dfl));
+    TRY(prepare(Q, doff, dfl, nullptr, st, flags | SAS_VALIDATE));
+    TRY(host_list_total(ho, st, fn, c.noun, c.hint, out_off, nq, capacity, out_total, &total));
+    if (total == 0) return 0;
+    for (int i = 0; i < nouts; i++) TRY(ho.twin_bytes(outs[i].ptr, total * outs[i].esz, outs[i].label, &out[i]));
+    TRY(scatter(out, total, st));
+    TRY(ho.copy_back(st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }

@@ -7,12 +7,18 @@
 //     and the output-centric tiling (csr_tile.hpp) of the candidates (one candidate = one
 //     occurrence of one piece) and of the elements of a CSR list (sas_align.hip: alignments,
 //     sas_map.hip: the bytes of a ragged batch);
-//   * the grid of the helper kernels and an event pair for the *_TIMING knobs;
+//   * the grid of the helper kernels, and what every verify stage does round its kernel: the
+//     read-back of the candidate total, the answer "nothing found", the verify grid, the
+//     *_TIMING knob (SeedTiming) and its event pair (SeedTimer);
 //   * declared here and defined once in seed_verify.hip: the index preconditions
-//     (seed_index_checks) and the seed stage up to the candidate offsets (seed_candidates).
+//     (seed_index_checks), the seed stage up to the candidate offsets (seed_candidates) and the
+//     one call path of the calls that return per-query lists in two passes (seed_list_call:
+//     sas_locate_mismatch, sas_locate_edit, sas_mems).
 #pragma once
 #include "call_io.hpp"
 #include "csr_tile.hpp"
+
+#include <functional>
 
 #define MM_BLOCK 256
 #define MM_T 2048          // candidates per tile
@@ -69,7 +75,49 @@ static inline dim3 seed_grid(const sas_index* x, uint64_t count) {
     return dim3(tile_grid(std::min(grid_for(count), (unsigned)x->num_cus * 8)));
 }
 
-// The event pair of SAS_MM_TIMING / SAS_ED_TIMING: nothing happens unless `on`; the events are
+// One total of a verify stage (the candidates coff[np], the proposals) read back; synchronises
+static inline int seed_read_total(const uint64_t* dev, hipStream_t st, uint64_t* total) {
+    HIP_TRY(hipMemcpyAsync(total, dev, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The answer of a batch without a candidate: nq + 1 zero offsets and a zero total (may be null)
+static inline int seed_nothing(uint64_t* out_off, uint64_t nq, uint64_t* out_total, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(out_off, 0, (nq + 1) * 8, st));
+    if (out_total) HIP_TRY(hipMemsetAsync(out_total, 0, 8, st));
+    return 0;
+}
+
+// The grid of a verify kernel over C candidates: one workgroup per tile of MM_T, at most
+// MM_MAX_GRID (they stride beyond), and SAS_TILE_GRID's cap
+static inline dim3 seed_verify_grid(uint64_t C) {
+    return dim3((unsigned)tile_grid(std::min<uint64_t>((C + MM_T - 1) / MM_T, MM_MAX_GRID)));
+}
+
+// A *_TIMING knob (<env>=1, read at every call: the stages are timed with HIP events, which
+// synchronises) and the calling thread's last figures for the extern "C" *_ms getters.  Slot 0:
+// the verify kernel and the candidates; slot 1 (sas_locate_edit): the de-duplication, proposals
+struct SeedTiming {
+    const char* env;
+    double ms[2] = {-1.0, -1.0};
+    uint64_t count[2] = {0, 0};
+    bool on() const {
+        const char* e = getenv(env);
+        return e && e[0] == '1';
+    }
+    void reset(uint64_t candidates) {
+        ms[0] = ms[1] = -1.0;
+        count[0] = candidates;
+        count[1] = 0;
+    }
+    double get(int slot, uint64_t* n) const {
+        if (n) *n = count[slot];
+        return ms[slot];
+    }
+};
+
+// The event pair of a SeedTiming knob: nothing happens unless `on`; the events are
 // destroyed on every way out.  stop() synchronises and gives the time since the last start()
 struct SeedTimer {
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -105,6 +153,37 @@ struct SeedTimer {
 // call's name, the head of every message
 int seed_index_checks(const std::string& w, const sas_index* x, uint32_t k, uint32_t flags, void* stream,
                       bool probe = true);
+
+// A call that returns per-query lists in two passes, as it describes itself to seed_list_call:
+// its name, its word in the host-pointer path's labels ("<label> queries"), the words of its
+// ENOSPC text (host_list_total) and, where it has one, a check of its own that follows the null test
+struct ListCall {
+    const char *fn, *label, *noun, *hint;
+    std::function<int()> check;
+};
+// One payload output: `capacity` elements of esz bytes; label: its twin's; required: null is
+// refused where the capacity is not 0
+struct ListOut {
+    void* ptr;
+    size_t esz;
+    const char* label;
+    bool required;
+};
+// Pass 1, all arrays on the device (out_qflags and out_total may be null): offsets, flags, total;
+// the callable keeps the scratch for pass 2.  flags: the call's, SAS_VALIDATE forced on host pointers
+typedef std::function<int(const MmQueries& Q, uint64_t* out_off, uint8_t* out_qflags, uint64_t* out_total,
+                          hipStream_t st, uint32_t flags)> ListPrepare;
+// Pass 2: the first `capacity` elements into the device arrays out[i] of ListOut i
+typedef std::function<int(void* const* out, uint64_t capacity, hipStream_t st)> ListScatter;
+
+// Such a call behind its own checks, in this order: the null test ("<fn>: null argument": out_off,
+// the queries, a required output, out_total on host pointers), the call's check, hipSetDevice, the
+// answer of nq == 0; then on device pointers prepare and scatter, on host pointers the staged queries, the
+// twins of out_off and out_qflags, prepare, host_list_total, and for a total above 0 the
+// payload's twins of `total` elements, scatter and the copy back
+int seed_list_call(const ListCall& c, const sas_index* x, const QueryArgs& q, uint64_t nq, uint64_t* out_off,
+                   uint8_t* out_qflags, const ListOut* outs, int nouts, uint64_t capacity, uint64_t* out_total,
+                   void* stream, uint32_t flags, const ListPrepare& prepare, const ListScatter& scatter);
 
 // Steps 1 to 4 of sas_mismatch.hip and sas_edit.hip, the scratch of which stays in the state:
 // the pieces, their gated SA ranges [lo, hi) and the candidate offsets coff (np + 1; the caller
